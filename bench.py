@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: audio samples/sec of FastSpeech2 + Parallel WaveGAN synthesis at 22.05 kHz.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
     (N > 1: either launched by the driver as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
      --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`, or plain `python bench.py --gpus N`, which
      re-executes itself under torch.distributed.run with N ranks on 127.0.0.1)
@@ -23,9 +23,12 @@ the engine's default 3-term split-fp16 MFMA evaluation of each fp32 product (mea
 exact-fp32 path's); the all-exact-fp32 configuration is timed as well and reported
 under `extras`.
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
-`roofline` (dominant kernel: the PWG residual block) and, at N = 1,
-`cpu_baseline` (the torch-CPU oracle on the host cores, bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the driver's contract
+fields (`value`, `ms_per_step`, ...).  `--dump-outputs DIR` first writes what the last timed step returned (rank 0)
+as DIR/<name>.npy.  `--full` adds everything else, outside the timed region: the pipeline check, the gather
+timings, `roofline` (dominant kernel: the PWG residual block), the other precisions and models (`extras`), at
+N = 1 `cpu_baseline` (the torch-CPU oracle on the host cores, bounded sample) and `parity_check`, and the
+sidecar file.
 """
 import argparse
 import json
@@ -702,6 +705,27 @@ def emit(full):
     print(short_line(full), flush=True)
 
 
+DUMP_LIMIT = 64 << 20   # bytes, all arrays of --dump-outputs together
+
+
+def dump_outputs(out_dir, wav, frames):
+    """--dump-outputs: what the last timed step returned to its caller -- the packed waveform of its (last) mini-batch,
+    float32, and the frame count of each utterance, float64 -- as <out_dir>/wav.npy and frames.npy.  A waveform above
+    DUMP_LIMIT (large --minibatch) is written as a fixed, seeded sample instead: wav_sample.npy at the sorted positions
+    wav_sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    w = wav.detach().float().cpu().numpy().ravel()
+    arrays = {"frames": np.asarray(frames, dtype=np.float64)}
+    room = (DUMP_LIMIT - arrays["frames"].nbytes) // 12          # float32 sample + float64 position each
+    if w.nbytes + arrays["frames"].nbytes <= DUMP_LIMIT:
+        arrays["wav"] = w
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(w.size, size=room, replace=False))
+        arrays["wav_sample"], arrays["wav_sample_index"] = w[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 
 _T0 = time.perf_counter()
 
@@ -734,6 +758,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo rehearsal of the multi-process orchestration with a stub in place of the engine "
                          "(test infrastructure; prints value null)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline line: pipeline check, gather timings, per-kernel "
+                         "roofline, --extras, CPU baseline and parity check, the sidecar file (off: set up, warm up, time, print)")
     args = ap.parse_args()
     if args.no_extras:
         args.extras = "none"
@@ -898,8 +927,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     _log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wav, frames)
     pipeline_check = None
-    if pipelined:
+    if pipelined and args.full:
         # back to the plain step for everything after the timed region; the pipelined waveform must be the plain one
         step = plain_step
         pending[0] = None
@@ -926,6 +957,7 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         elapsed = float(t.item())                   # `value` follows the slowest rank
         rank_ms = {"min": float(tmin.item()) / args.steps * 1e3, "max": elapsed / args.steps * 1e3}   # load imbalance
+    if distributed and args.full:
         # result collection: every rank's packed waveform of its last mini-batch gathered on rank 0 --
         # one all_gather of the lengths + direct sends of the exact sizes (gather_ragged_to); timed on its own, never part
         # of `value`.  The all-ranks variant (padded all_gather) is timed next to it for consumers that need that.
@@ -966,6 +998,59 @@ def main():
                 "gather_all_ms": gather_all_ms, "rccl_world_size": comm_world, "rank_ms_per_step": rank_ms,
                 "config": {"global_batch": global_batch, "utterances_this_rank": len(own),
                            "minibatches_per_step": len(chunks), "collectives": collectives}}), flush=True)
+        if distributed:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    def headline():
+        """The record's contract fields: what the K timed steps gave, and the workload they ran."""
+        total_samples = global_batch * per_utt             # whole job, all ranks, per step
+        ms_per_step = elapsed / args.steps * 1e3
+        value = total_samples * args.steps / elapsed
+        return {
+            "metric": "audio samples/sec, FastSpeech2+PWGAN 22.05kHz",
+            "value": value,
+            "unit": "samples/s",
+            "x_realtime": value / SAMPLE_RATE,
+            "rtf_reference_convention": SAMPLE_RATE / value,
+            "n_gpus": world,
+            "rccl_world_size": comm_world,
+            "rank_ms_per_step": rank_ms,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32 (3-term split-fp16 MFMA, fp32-equivalent; exact-fp32 in roofline.exact_f32)",
+            "dtype_note": "fp32 storage and accumulation everywhere; the dense contractions (PWG residual blocks and "
+                          "last convs, FastSpeech2 Linear/Conv1D/attention) evaluate each fp32 product as a 3-term split-fp16 "
+                          "MFMA sum (a_hi*b_hi + a_lo*b_hi + a_hi*b_lo) of BLOCK-SCALED operands (DESIGN.md 3 / HISTORY 4.7): the "
+                          "error is the exact-fp32 MFMA path's independent of the magnitude of weights or activations; "
+                          "parity_check compares this very batch with the fp32 CPU oracle; softmax / LayerNorm / durations are "
+                          "plain fp32; the all-exact-fp32 configuration is timed as roofline.exact_f32",
+            "data": "synthetic",
+            "config": {
+                "workload": "FastSpeech2+PWG end-to-end (BASELINE config 4 per-GPU share): "
+                            f"{UTT_PER_GPU} utterances/GPU x {TOKENS} phonemes -> {TOKENS * FRAMES_PER_TOKEN} frames "
+                            f"-> {TOKENS * FRAMES_PER_TOKEN * HOP} samples each, LJSpeech architecture, random-init weights",
+                "utterances_per_gpu": len(own),
+                "global_batch": global_batch,
+                "minibatch": mb,
+                "parallelism": f"dp{world} (utterance sharding, no data-path collective)",
+                "collectives": collectives,
+                "pipeline": ("next batch's acoustic model (second engine handle, own side stream) issued before this batch's vocoder" if two_lanes
+                             else "next batch's acoustic model issued on a side stream under this batch's vocoder") if pipelined else "none",
+            },
+        }
+
+    if not args.full:
+        if rank == 0:
+            _log("the line")
+            print(short_line(headline()), flush=True)
+        _log("done")
         if distributed:
             import torch.distributed as dist
             dist.barrier()
@@ -1067,9 +1152,6 @@ def main():
 
     full = None
     if rank == 0:
-        total_samples = global_batch * per_utt             # whole job, all ranks, per step
-        ms_per_step = elapsed / args.steps * 1e3
-        value = total_samples * args.steps / elapsed
         layer_key = next((k for k in ("pwg_layer_h3", "pwg_layer_b3", "pwg_layer") if k in prof), "pwg_layer")
         n_layer, ms_layer = prof.get(layer_key, (0, 0.0))
         avg_ms = ms_layer / max(n_layer, 1)
@@ -1102,41 +1184,8 @@ def main():
             achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
             roof = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0}
         total_prof_ms = sum(ms for _, ms in prof.values()) / prof_steps
-        full = {
-            "metric": "audio samples/sec, FastSpeech2+PWGAN 22.05kHz",
-            "value": value,
-            "unit": "samples/s",
-            "x_realtime": value / SAMPLE_RATE,
-            "rtf_reference_convention": SAMPLE_RATE / value,
-            "n_gpus": world,
-            "rccl_world_size": comm_world,
-            "rank_ms_per_step": rank_ms,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32 (3-term split-fp16 MFMA, fp32-equivalent; exact-fp32 in roofline.exact_f32)",
-            "dtype_note": "fp32 storage and accumulation everywhere; the dense contractions (PWG residual blocks and "
-                          "last convs, FastSpeech2 Linear/Conv1D/attention) evaluate each fp32 product as a 3-term split-fp16 "
-                          "MFMA sum (a_hi*b_hi + a_lo*b_hi + a_hi*b_lo) of BLOCK-SCALED operands (DESIGN.md 3 / HISTORY 4.7): the "
-                          "error is the exact-fp32 MFMA path's independent of the magnitude of weights or activations; "
-                          "parity_check compares this very batch with the fp32 CPU oracle; softmax / LayerNorm / durations are "
-                          "plain fp32; the all-exact-fp32 configuration is timed as roofline.exact_f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "FastSpeech2+PWG end-to-end (BASELINE config 4 per-GPU share): "
-                            f"{UTT_PER_GPU} utterances/GPU x {TOKENS} phonemes -> {TOKENS * FRAMES_PER_TOKEN} frames "
-                            f"-> {TOKENS * FRAMES_PER_TOKEN * HOP} samples each, LJSpeech architecture, random-init weights",
-                "utterances_per_gpu": len(own),
-                "global_batch": global_batch,
-                "minibatch": mb,
-                "parallelism": f"dp{world} (utterance sharding, no data-path collective)",
-                "collectives": collectives,
-                "pipeline": ("next batch's acoustic model (second engine handle, own side stream) issued before this batch's vocoder" if two_lanes
-                             else "next batch's acoustic model issued on a side stream under this batch's vocoder") if pipelined else "none",
-            },
+        full = headline()
+        full.update({
             "roofline": dict(roof, **{
                 "kernel": {"pwg_layer": "k_pwg_layer (exact fp32 MFMA)", "pwg_layer_h3": "k_pwg_layer_b3<HALF> (3-term split-fp16 MFMA)",
                            "pwg_layer_b3": "k_pwg_layer_b3 (3-term split-bf16 MFMA)"}[layer_key] +
@@ -1154,7 +1203,7 @@ def main():
             }),
             "kernel_ms_per_step": {k: ms / prof_steps for k, (_, ms) in sorted(prof.items())},
             "kernel_ms_sum": total_prof_ms,
-        }
+        })
         ex32 = extras.get("all_exact_f32_mfma")
         if ex32 and ex32.get("layer_kernel_avg_ms"):
             # the strict-fp32 configuration of the SAME step (every contraction on v_mfma_f32_32x32x2_f32): its layer kernel is

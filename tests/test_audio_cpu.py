@@ -65,9 +65,9 @@ def test_write_wav_roundtrip(tmp_path):
 
 
 def test_spec_normalizers_match_reference_source():
-    """LogMagnitude / UnitMagnitude (parakeet/audio/spec_normalizer.py:39-75): the reference file itself is numpy-only, so it is
-    executed here when /root/reference is present; its formulas are also checked through their defining properties."""
-    import importlib.util
+    """LogMagnitude / UnitMagnitude (parakeet/audio/spec_normalizer.py:39-75): against the outputs of the reference file itself
+    (numpy-only; tools/make_golden_audio.py -> tests/golden/spec_normalizer.npz); their formulas are also checked through their
+    defining properties."""
     import os
     from parakeet_amd.audio import LogMagnitude, UnitMagnitude
     rng = np.random.default_rng(3)
@@ -80,11 +80,8 @@ def test_spec_normalizers_match_reference_source():
     assert np.allclose(um.transform(np.array([1e-4, 10.0 ** (-4 + 100 / 20)])), [0.0, 1.0])   # -80 dB - 20 -> 0; +20 dB - 20 -> 1
     inside = (u > 0) & (u < 1)
     assert np.allclose(um.inverse(u)[inside], x[inside], rtol=1e-10)
-    path = "/root/reference/parakeet/audio/spec_normalizer.py"
-    if os.path.exists(path):
-        spec = importlib.util.spec_from_file_location("ref_spec_normalizer", path)
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-        for mine, theirs in ((lm, ref.LogMagnitude()), (um, ref.UnitMagnitude())):
-            assert np.array_equal(mine.transform(x), theirs.transform(x))
-            assert np.array_equal(mine.inverse(mine.transform(x)), theirs.inverse(theirs.transform(x)))
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spec_normalizer.npz"))
+    x = gold["x"]
+    for name, mine in (("log", lm), ("unit", um)):
+        assert np.array_equal(mine.transform(x), gold[name + "_transform"])
+        assert np.array_equal(mine.inverse(mine.transform(x)), gold[name + "_inverse"])

@@ -14,7 +14,7 @@ def _run(*extra, env=None):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     e.update(env or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--steps", "2", "--warmup", "1",
                         *extra], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -114,3 +114,38 @@ def _strings(o):
     elif isinstance(o, list):
         for v in o:
             yield from _strings(v)
+
+
+def test_plain_run_is_the_timed_steps_and_dumps_their_outputs(tmp_path):
+    """Without --full the run times --steps steps and prints the contract fields only (no gather, no sidecar); --dump-outputs
+    writes what the last timed step returned: the packed waveform (float32) and the frame counts (float64)."""
+    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    out = json.loads(r.stdout.decode().rstrip("\n").splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0.0
+    assert "gather_ms" not in out and "sidecar" not in out and "roofline" not in out
+    import numpy as np
+    assert sorted(os.listdir(tmp_path / "out")) == ["frames.npy", "wav.npy"]
+    wav, frames = np.load(tmp_path / "out" / "wav.npy"), np.load(tmp_path / "out" / "frames.npy")
+    assert wav.dtype == np.float32 and wav.shape == (32 * 640 * 256,)
+    assert frames.dtype == np.float64 and frames.tolist() == [640.0] * 32
+
+
+def test_dump_of_a_large_output_is_a_fixed_sample_under_the_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    wav = torch.arange(bench.DUMP_LIMIT // 4 + 1000, dtype=torch.float32)
+    frames = np.full(4, 7, np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), wav, frames)
+    names = ["frames.npy", "wav_sample.npy", "wav_sample_index.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= bench.DUMP_LIMIT + 3 * 128     # (+ .npy headers)
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(np.array_equal(a[n], np.load(tmp_path / "b" / n)) for n in names)                # same sample every run
+    idx = a["wav_sample_index.npy"]
+    assert np.all(np.diff(idx) > 0) and np.array_equal(a["wav_sample.npy"], wav.numpy()[idx.astype(np.int64)])

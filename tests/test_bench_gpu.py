@@ -18,7 +18,7 @@ def _bench(*extra, env=None):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     e.update(env or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-extras",
                         "--no-cpu-baseline", *extra], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -58,7 +58,7 @@ def test_under_torch_distributed_run_strong_scaling():
     e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-extras", "--no-cpu-baseline", "--scaling", "strong", "--global-batch", "64"]
+           "--full", "--no-extras", "--no-cpu-baseline", "--scaling", "strong", "--global-batch", "64"]
     r = subprocess.run(cmd, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -66,3 +66,25 @@ def test_under_torch_distributed_run_strong_scaling():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["scaling"] == "strong" and out["config"]["utterances_per_gpu"] == 64
     assert out["gather_ms"] is not None and out["gather_ms"] >= 0.0 and out["value"] > 1e6
+
+
+def _bench_plain(*args):
+    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
+                                                          "PK_BENCH_FORCE_DIST")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args], env=e,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    return json.loads(r.stdout.decode().rstrip("\n").splitlines()[-1])
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain run (no --full): set-up, warm-up, the timed steps, the line; --dump-outputs holds the last timed step's packed
+    waveform of the 32 benchmark utterances and their frame counts."""
+    import numpy as np
+    out = _bench_plain("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 3 and out["value"] > 1e6 and out["higher_is_better"] is True and out["unit"] == "samples/s"
+    assert abs(out["ms_per_step"] * 1e-3 * out["value"] - 32 * 163840) < 1.0
+    assert "roofline" not in out and "cpu_baseline" not in out and "pipeline_check" not in out
+    wav, frames = np.load(tmp_path / "wav.npy"), np.load(tmp_path / "frames.npy")
+    assert wav.dtype == np.float32 and wav.shape == (32 * 163840,) and np.isfinite(wav).all() and np.abs(wav).max() > 0
+    assert frames.dtype == np.float64 and frames.tolist() == [640.0] * 32

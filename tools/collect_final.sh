@@ -12,7 +12,7 @@ timeout 200 python -m pytest tests/test_tts_gpu.py tests/test_taco2_gpu.py tests
 tail -3 $OUT/tests.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp
-timeout 300 python $R/bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 300 python $R/bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 head -c 600 $OUT/bench.json; echo
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
 for m in tts taco; do

@@ -13,7 +13,7 @@ cd $R
 (timeout 800 python -m pytest tests -m gpu -q --timeout=300 2>&1 | tail -25) > $OUT/gputest.txt
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 cd /tmp
-timeout 300 python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_tts -o tts -- python $R/tools/quick_ar.py tts 32 640 > $OUT/quick_tts.log 2>&1
 find $OUT -name "*kernel_stats.csv" | while read f; do cp $f $OUT/$(basename $f); done

@@ -13,7 +13,7 @@ timeout 900 python -m pytest tests -m gpu -q -rA --durations=25 --timeout=300 > 
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests.log | tail -40
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp
-timeout 420 python $R/bench.py --steps 20 --warmup 5 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 420 python $R/bench.py --full --steps 20 --warmup 5 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 head -c 600 $OUT/bench.json; echo
 python - <<PY
 import json

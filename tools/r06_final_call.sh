@@ -15,7 +15,7 @@ timeout 1800 python -m pytest tests -m gpu -q -rA --durations=25 --timeout=600 >
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests.log | tail -20
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp
-timeout 500 python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.stdout 2> $OUT/bench.err
+timeout 500 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.stdout 2> $OUT/bench.err
 tail -1 $OUT/bench.stdout > $OUT/bench.json; wc -c $OUT/bench.json; cat $OUT/bench.json; echo
 cp $R/profiles/bench_extras_last.json $OUT/bench_extras_last.json 2>/dev/null
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --extras none > $OUT/stats.log 2>&1

@@ -12,7 +12,7 @@ timeout 300 tools/micro/mfma_chain_hazard 2000 > $OUT/mfma_chain_hazard.txt 2>&1
 timeout 1200 python -m pytest tests/test_benchshape_golden_gpu.py tests/test_waveflow_gpu.py tests/test_bench_gpu.py tests/test_pwg_gpu.py -m gpu -q -rA --durations=20 --timeout=600 > $OUT/tests_new.log 2>&1
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests_new.log | tail -40
 cd /tmp
-timeout 400 python $R/bench.py > $OUT/bench.stdout 2> $OUT/bench.err
+timeout 400 python $R/bench.py --full > $OUT/bench.stdout 2> $OUT/bench.err
 tail -1 $OUT/bench.stdout > $OUT/bench.json; wc -c $OUT/bench.json; cat $OUT/bench.json; echo
 cp $R/profiles/bench_extras_last.json $OUT/bench_extras_last.json 2>/dev/null
 tail -5 $OUT/bench.err

@@ -15,7 +15,7 @@ timeout 1500 python -m pytest tests -m gpu -q -rA --durations=60 --timeout=300 >
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests.log | tail -40
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp
-timeout 300 python $R/bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 300 python $R/bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 head -c 700 $OUT/bench.json; echo
 for kv in 0 1; do
   PK_TTS_KV_PREFIX=$kv timeout 120 python $R/tools/quick_ar.py tts 32 640 > $OUT/quick_tts_kv$kv.log 2>&1

@@ -12,7 +12,7 @@ timeout 700 python -m pytest tests/test_pwg_gpu.py tests/test_benchshape_gpu.py 
 grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests.log | tail -20
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 cd /tmp
-timeout 600 python $R/bench.py 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 600 python $R/bench.py --full 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 head -c 400 $OUT/bench.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
 find $OUT/stats -name "*kernel_stats.csv" | while read f; do cp $f $OUT/bench_kernel_stats.csv; done
