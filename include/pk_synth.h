@@ -18,6 +18,7 @@
  *   pk_tts_*    parakeet/models/transformer_tts/transformer_tts.py TransformerTTS.inference :511-647,
  *               TransformerTTSInference.forward :757-767
  *   pk_taco_*   parakeet/models/tacotron2.py Tacotron2.infer :781-840 (Tacotron2Decoder.infer :474-541)
+ *   pk_spk_*    parakeet/models/lstm_speaker_encoder.py LSTMSpeakerEncoder.embed_sequences / embed_utterance :40-53
  *   pk_stft_mel parakeet/modules/audio.py STFT.magnitude :202-215 + MelScale :226-229,
  *               parakeet/data/get_feats.py LogMelFBank.get_log_mel_fbank :80-88
  *
@@ -525,6 +526,35 @@ int pk_taco_read(pk_taco* h, float* mel_output, float* mel_outputs_postnet, floa
 /* Test tap of the last infer: 0 = encoder outputs (T_b, d_encoder). */
 int pk_taco_debug_read(pk_taco* h, int32_t what, int32_t b, float* host_out, int64_t n_floats);
 void pk_taco_destroy(pk_taco* h);
+
+/* ------------------------------------------------------- GE2E speaker encoder */
+/* LSTMSpeakerEncoder(n_mels, num_layers, hidden_size, output_size) -- parakeet/models/lstm_speaker_encoder.py:24-53
+ * (released config examples/ge2e/config.py: 40, 3, 256, 256).  Inference only (embed_sequences / embed_utterance).
+ * Refused with PK_EUNSUPPORTED: hidden_size not a multiple of 32 or above 512, output_size not a multiple of 32 or above
+ * 4096, n_mels above 4096. */
+typedef struct {
+    int32_t n_mels, num_layers, hidden_size, output_size;
+} pk_spk_cfg;
+typedef struct pk_spk pk_spk;
+
+int pk_spk_create(pk_ctx* ctx, const pk_spk_cfg* cfg, pk_spk** out);
+/* set_state_dict entry: lstm.weight_ih_l{k} / weight_hh_l{k} / bias_ih_l{k} / bias_hh_l{k} (or their aliases
+ * lstm.{k}.cell.weight_ih ...; the first form wins when both are given), linear.weight [in, out], linear.bias.
+ * Other names (similarity_weight / similarity_bias: training only) are stored and ignored. */
+int pk_spk_set_param(pk_spk* h, const char* name, const float* data, const int64_t* shape, int32_t ndim);
+/* 0 = exact fp32 MFMA, 1 = 3-term split-fp16 MFMA (default, as pk_taco_set_math). */
+int pk_spk_set_math(pk_spk* h, int32_t mode);
+int pk_spk_finalize(pk_spk* h);
+/* embed_sequences (:40-48) of P partials of T frames, all pointers but cu_partials on the DEVICE:
+ *   partials  (P, T, n_mels) float32
+ *   h0, c0    (num_layers, P, hidden_size) initial states, or both NULL (zeros)
+ *   cu_partials HOST (U + 1): utterance u = partials cu[u] .. cu[u + 1] - 1 -> out (U, output_size) = embed_utterance of
+ *             each (:50-53: mean of the normalised partial embeddings, normalised again); NULL: U == P and out (P,
+ *             output_size) = the normalised partial embeddings.
+ * A partial's embedding does not depend on the other partials of the call. */
+int pk_spk_embed(pk_spk* h, const float* partials, int32_t P, int32_t T, const float* h0, const float* c0,
+                 const int32_t* cu_partials, int32_t U, float* out);
+void pk_spk_destroy(pk_spk* h);
 
 /* ------------------------------------------------- STFT / mel / log features */
 /* parakeet/modules/audio.py STFT (:74-215) + MelScale (:218-229); host twin

@@ -91,6 +91,10 @@ class TacoCfg(C.Structure):
         "use_stop_token")] + [("p_prenet_dropout", C.c_float)]
 
 
+class SpkCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "num_layers", "hidden_size", "output_size")]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -181,6 +185,12 @@ def _declare(lib):
         "pk_taco_read": (C.c_int, [vp, f32p, f32p, f32p, f32p, i32]),
         "pk_taco_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_taco_destroy": (None, [vp]),
+        "pk_spk_create": (C.c_int, [vp, C.POINTER(SpkCfg), C.POINTER(vp)]),
+        "pk_spk_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),
+        "pk_spk_set_math": (C.c_int, [vp, i32]),
+        "pk_spk_finalize": (C.c_int, [vp]),
+        "pk_spk_embed": (C.c_int, [vp, f32p, i32, i32, f32p, f32p, i32p, i32, f32p]),
+        "pk_spk_destroy": (None, [vp]),
         "pk_mel_create": (C.c_int, [vp, C.POINTER(MelCfg), f32p, f32p, C.POINTER(vp)]),
         "pk_mel_num_frames": (C.c_int, [vp, i32, i32p]),
         "pk_mel_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32, i32]),

@@ -303,3 +303,14 @@ def load_tacotron2(config, checkpoint_path):
     model.set_state_dict(load_params(path if path.endswith(".pdparams") else path + ".pdparams"))
     model.eval()
     return model
+
+
+def load_ge2e(path, n_mels=40, num_layers=3, hidden_size=256, output_size=256):
+    """The GE2E speaker encoder from a ``step-N.pdparams`` file (examples/ge2e/inference.py:58-65; ``path`` with or
+    without the suffix), released shape by default (examples/ge2e/config.py)."""
+    from .lstm_speaker_encoder import LSTMSpeakerEncoder
+    path = str(path)
+    model = LSTMSpeakerEncoder(n_mels, num_layers, hidden_size, output_size)
+    model.set_state_dict(load_params(path if path.endswith(".pdparams") else path + ".pdparams"))
+    model.eval()
+    return model

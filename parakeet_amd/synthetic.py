@@ -539,3 +539,30 @@ def tacotron2_state(cfg=None, seed=2222, stop_bias=0.0, stop_gain=1.0, lstm_alia
     for j in range(n):
         conv_bn(f"postnet.conv_batchnorms.{j}", M if j == n - 1 else C, M if j == 0 else C, kf)
     return st
+
+
+GE2E_RELEASED = dict(n_mels=40, num_layers=3, hidden_size=256, output_size=256)   # examples/ge2e/config.py
+
+
+def ge2e_state(cfg=None, seed=1234, lstm_aliases=True):
+    """LSTMSpeakerEncoder state dict (parakeet/models/lstm_speaker_encoder.py:24-32) with Paddle's default initialisers:
+    LSTM weights and biases U(-1/sqrt(H), 1/sqrt(H)), ``linear`` Xavier-uniform weight [in, out] and zero bias,
+    similarity_weight 10, similarity_bias -5.  ``lstm_aliases`` adds the "lstm.{k}.cell.*" names next to the
+    "lstm.*_l{k}" ones, as a Paddle state dict carries both."""
+    cfg = dict(GE2E_RELEASED, **(cfg or {}))
+    rng = np.random.default_rng(seed)
+    H, O = cfg["hidden_size"], cfg["output_size"]
+    k = 1.0 / math.sqrt(H)
+    st = {}
+    for layer in range(cfg["num_layers"]):
+        isz = cfg["n_mels"] if layer == 0 else H
+        for name, shape in (("weight_ih", (4 * H, isz)), ("weight_hh", (4 * H, H)), ("bias_ih", (4 * H,)),
+                            ("bias_hh", (4 * H,))):
+            st[f"lstm.{name}_l{layer}"] = rng.uniform(-k, k, size=shape).astype(np.float32)
+            if lstm_aliases:
+                st[f"lstm.{layer}.cell.{name}"] = st[f"lstm.{name}_l{layer}"]
+    st["linear.weight"] = _xavier(rng, (H, O))
+    st["linear.bias"] = np.zeros(O, dtype=np.float32)
+    st["similarity_weight"] = np.array([10.0], dtype=np.float32)
+    st["similarity_bias"] = np.array([-5.0], dtype=np.float32)
+    return st
