@@ -102,21 +102,24 @@ int pk_prof_dump(pk_ctx* ctx, char* buf, int64_t buflen);
 
 /* ------------------------------------------------------ Parallel WaveGAN */
 /* Constructor arguments of PWGGenerator (parallel_wavegan.py:369-388) that
- * change device work.  Unsupported combinations -> PK_EUNSUPPORTED. */
+ * change device work.  Unsupported combinations -> PK_EUNSUPPORTED (the message names the limit).
+ * The default 1/1/3/64/128/64/80 runs the tuned kernels (pwg.hip); every other shape inside the
+ * envelope below runs the shape-generic kernels (pwg_gen.hip; also the default one under option
+ * "generic_kernel"). */
 typedef struct {
-    int32_t in_channels;        /* 1 */
-    int32_t out_channels;       /* 1 */
-    int32_t kernel_size;        /* 3 */
-    int32_t layers;             /* 30, must be a multiple of stacks (:398) */
+    int32_t in_channels;        /* 1 only */
+    int32_t out_channels;       /* 1 only */
+    int32_t kernel_size;        /* 3; odd, 1 ... 9 (padding (k-1)/2 * dilation) */
+    int32_t layers;             /* 30, must be a multiple of stacks (:398); dilation 2^(layers/stacks - 1) <= 2^11 */
     int32_t stacks;             /* 3  */
-    int32_t residual_channels;  /* 64 */
-    int32_t gate_channels;      /* 128 */
-    int32_t skip_channels;      /* 64 */
-    int32_t aux_channels;       /* 80 */
+    int32_t residual_channels;  /* 64; a multiple of 16, 16 ... 256 */
+    int32_t gate_channels;      /* 128; 32 ... 512 with gate_channels / 2 a multiple of 16 */
+    int32_t skip_channels;      /* 64; a multiple of 16, 16 ... 256 */
+    int32_t aux_channels;       /* 80; 1 ... 512 */
     int32_t aux_context_window; /* 2 */
     int32_t n_upsample;         /* 4 */
     int32_t upsample_scales[8]; /* 4,4,4,4 (LJSpeech, hop 256) or 4,5,3,5 (baker / vctk, hop 300); any product 32..1024 */
-    int32_t use_causal_conv;    /* 0 only */
+    int32_t use_causal_conv;    /* 0 only (the reference's causal branch cannot run, :305) */
 } pk_pwg_cfg;
 
 int pk_pwg_create(pk_ctx* ctx, const pk_pwg_cfg* cfg, pk_pwg** out);
@@ -172,6 +175,11 @@ int pk_pwg_set_chunk_samples(pk_pwg* h, int64_t samples);
  *                  pk_pwg_finalize -- no first_conv launch, no x planes for layer 0 (round 6); 0 = first_conv, then the ordinary first block.
  *                  Both are within the engine's error bars of the reference; they differ from each other in the last bits.
  *   "scale_guard_every"  the sampling period under "scale_guard" 1 (default 16; 0 = never re-sample).
+ *   "generic_kernel"  1 = run the default shape on the shape-generic kernels as well (pwg_gen.hip; other shapes always
+ *                  do); 0 (default) = the tuned kernels.  Takes effect at the next pk_pwg_finalize.  On the generic path
+ *                  x is fp32 with a measured scale per 32-sample block under both split maths (the "planes" = 0 scheme):
+ *                  "planes", "scale_guard", "scale_guard_every" and "noise_fed_first" are accepted and have no effect,
+ *                  pk_pwg_scale_overshoot returns PK_ESTATE and debug tap 3 PK_EUNSUPPORTED.
  *                  pk_pwg_scale_overshoot reports what was measured. */
 int pk_pwg_set_option(pk_pwg* h, const char* key, int64_t value);
 /* log2(a-priori bound / measured max|x|) per layer input, l = 0 .. layers (n = layers + 1 floats), the maximum over the
@@ -192,9 +200,9 @@ int pk_pwg_finalize(pk_pwg* h);
 int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, int32_t B,
                  const float* noise, float* wav, int32_t flags);
 /* Debug / test taps: copy internal activations of the LAST pk_pwg_infer call
- * for utterance b to host.  what: 0 = layer 0's conv1x1_aux(upsampled c) (gate, S_b),
- * 1 = residual-stack output x (residual, S_b), 2 = skip sum before the sqrt(1/layers)
- * scale (skip, S_b), all channel-major. */
+ * for utterance b to host.  what: 0 = layer 0's conv1x1_aux(upsampled c) (gate_channels, S_b),
+ * 1 = residual-stack output x (residual_channels, S_b), 2 = skip sum before the sqrt(1/layers)
+ * scale (skip_channels, S_b), all channel-major. */
 int pk_pwg_debug_read(pk_pwg* h, int32_t what, int32_t b, float* host_out, int64_t n_floats);
 void pk_pwg_destroy(pk_pwg* h);
 

@@ -40,6 +40,7 @@
 
 #include "pk_gemm.h"
 #include "pk_split.h"
+#include "pwg_gen.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1613,6 +1614,12 @@ struct pk_pwg {
     pk_dbuf ws_amax;
     unsigned long long seed = 0, rng_offset = 0;   // internal noise stream (noise == NULL)
     long chunk_samples = 1L << 40;                  // residual-stack chunk (env PK_PWG_CHUNK_SAMPLES); default: one chunk
+    // the shape-generic path (pwg_gen.hip): every configuration the kernels above are not built for, and the default one
+    // under option "generic_kernel" (read at pk_pwg_finalize; gen_active says which path the finalized weights are for)
+    bool generic_shape = false;
+    bool generic_opt = false;
+    bool gen_active = false;
+    pwg_gen* gen = nullptr;
 };
 
 // Timing ablations of the layer kernel (PK_PWG_ABLATE -> pk_pwg::dbg; results are WRONG): instantiated in the profile build only
@@ -1637,14 +1644,11 @@ extern "C" int pk_pwg_create(pk_ctx* ctx, const pk_pwg_cfg* cfg, pk_pwg** out) {
         PK_FAIL(PK_ESHAPE, "PWGGenerator: layers (%d) must be a positive multiple of stacks (%d)",
                 cfg->layers, cfg->stacks);  // assert layers % stacks == 0 (:398)
     if (cfg->use_causal_conv) PK_FAIL(PK_EUNSUPPORTED, "PWGGenerator: use_causal_conv=True is not implemented");
-    if (cfg->in_channels != 1 || cfg->out_channels != 1 || cfg->kernel_size != KTAP ||
-        cfg->residual_channels != R || cfg->gate_channels != G || cfg->skip_channels != SK ||
-        cfg->aux_channels != AUX)
-        PK_FAIL(PK_EUNSUPPORTED,
-                "PWGGenerator: kernels are built for in/out 1, kernel 3, residual 64, gate 128, "
-                "skip 64, aux 80 (got %d/%d, k%d, %d, %d, %d, %d)",
-                cfg->in_channels, cfg->out_channels, cfg->kernel_size, cfg->residual_channels,
-                cfg->gate_channels, cfg->skip_channels, cfg->aux_channels);
+    // the tuned kernels take in/out 1, kernel 3, residual 64, gate 128, skip 64, aux 80; the generic path the envelope of pwg_gen_check
+    const bool generic_shape = cfg->in_channels != 1 || cfg->out_channels != 1 || cfg->kernel_size != KTAP ||
+                               cfg->residual_channels != R || cfg->gate_channels != G || cfg->skip_channels != SK ||
+                               cfg->aux_channels != AUX;
+    if (generic_shape) PK_TRY(pwg_gen_check(*cfg));
     if (cfg->n_upsample < 1 || cfg->n_upsample > 8) PK_FAIL(PK_EINVAL, "PWGGenerator: 1..8 upsample scales");
     int hop = 1;
     double reach = 0.0;  // of the composite upsampler, in frames
@@ -1670,6 +1674,7 @@ extern "C" int pk_pwg_create(pk_ctx* ctx, const pk_pwg_cfg* cfg, pk_pwg** out) {
     h->max_dilation = 1 << (lps - 1);
     h->gap = ((h->max_dilation + TILE - 1) / TILE) * TILE;
     if (h->gap < TILE) h->gap = TILE;
+    h->generic_shape = generic_shape;
     if (const char* e = pk_prof_env("PK_PWG_ABLATE")) h->dbg = atoi(e);   // profile build only: results are wrong when set
     if (const char* e = pk_prof_env("PK_PWG_PLANES")) h->planes_on = e[0] != '0';   // PK_PWG_PLANES=0: x as fp32 with per-block scales (round 2)
     if (const char* e = pk_prof_env("PK_PWG_CHUNK_SAMPLES")) h->chunk_samples = std::max(1L, atol(e));
@@ -1692,7 +1697,8 @@ extern "C" int pk_pwg_set_normalizer(pk_pwg* h, const float* mu, const float* si
         h->use_norm = false;
         return PK_OK;
     }
-    if (!mu || !sigma || n != AUX) PK_FAIL(PK_ESHAPE, "normalizer needs mu and sigma of %d elements", AUX);
+    if (!mu || !sigma || n != h->cfg.aux_channels)
+        PK_FAIL(PK_ESHAPE, "normalizer needs mu and sigma of %d elements", h->cfg.aux_channels);
     h->h_mu.assign(mu, mu + n);
     h->h_sigma.assign(sigma, sigma + n);
     h->use_norm = true;
@@ -1775,6 +1781,10 @@ extern "C" int pk_pwg_set_option(pk_pwg* h, const char* key, int64_t value) {
     } else if (strcmp(key, "noise_fed_first") == 0) {
         if (value < 0 || value > 1) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: noise_fed_first %lld (0, 1)", (long long)value);
         h->noise_fed = value != 0;
+    } else if (strcmp(key, "generic_kernel") == 0) {
+        if (value < 0 || value > 1) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: generic_kernel %lld (0, 1)", (long long)value);
+        h->generic_opt = value != 0;
+        h->finalized = false;     // takes effect at the next pk_pwg_finalize
     } else if (strcmp(key, "scale_guard_every") == 0) {
         if (value < 0 || value > (1 << 30)) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: scale_guard_every %lld", (long long)value);
         h->guard_every = (int)value;
@@ -1784,6 +1794,7 @@ extern "C" int pk_pwg_set_option(pk_pwg* h, const char* key, int64_t value) {
 
 extern "C" int pk_pwg_scale_overshoot(pk_pwg* h, float* log2_overshoot, int32_t n, int32_t* fell_back) {
     if (!h || !log2_overshoot) PK_FAIL(PK_EINVAL, "pk_pwg_scale_overshoot: NULL argument");
+    if (h->gen_active) PK_FAIL(PK_ESTATE, "pk_pwg_scale_overshoot: the generic path has no scale guard");
     {
         pk_device_guard _dg(h->ctx->device);
         pwg_poll_sample(h, true);    // a sample still in flight is waited for: the report is of the LAST guarded or sampled call
@@ -1888,6 +1899,15 @@ extern "C" int pk_pwg_finalize(pk_pwg* h) {
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     const pk_pwg_cfg& c = h->cfg;
+    if (h->generic_shape || h->generic_opt) {
+        h->finalized = false;
+        h->gen_active = false;
+        PK_TRY(pwg_gen_finalize(&h->gen, ctx, c, h->params, h->hop));
+        h->gen_active = true;
+        h->finalized = true;
+        return PK_OK;
+    }
+    h->gen_active = false;
     std::vector<float> w, b;
     // first_conv
     PK_TRY(pk_get_weight(h->params, "first_conv", {R, 1, 1}, w));
@@ -2160,6 +2180,20 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
     if (B <= 0) PK_FAIL(PK_EINVAL, "pk_pwg_infer: batch size must be positive");
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
+    if (h->gen_active) {
+        pwg_gen_call k;
+        k.ctx = ctx;
+        k.cfg = &h->cfg;
+        k.hop = h->hop;
+        k.math = h->math;
+        k.use_norm = h->use_norm;
+        k.mu = h->d_mu.as<float>();
+        k.sigma = h->d_sigma.as<float>();
+        k.seed = h->seed;
+        k.rng_offset = &h->rng_offset;
+        k.chunk_samples = h->chunk_samples;
+        return pwg_gen_infer(h->gen, k, mel, frames, B, noise, wav, flags);
+    }
     pwg_poll_sample(h, false);   // the verdict of an earlier sampled call, if its copies have landed (never waits)
     const pk_pwg_cfg& c = h->cfg;
     const int hop = h->hop, gap = h->gap;
@@ -2592,6 +2626,10 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
 
 extern "C" int pk_pwg_debug_read(pk_pwg* h, int32_t what, int32_t b, float* host_out, int64_t n_floats) {
     if (!h || !host_out) PK_FAIL(PK_EINVAL, "pk_pwg_debug_read: NULL argument");
+    if (h->gen_active) {
+        PK_DEVICE(h->ctx->device);
+        return pwg_gen_debug_read(h->gen, h->ctx, what, b, host_out, n_floats);
+    }
     if (h->last_Ttot == 0) PK_FAIL(PK_ESTATE, "pk_pwg_debug_read: no inference has run");
     if (b < 0 || b >= (int)h->last_frames.size()) PK_FAIL(PK_EINVAL, "pk_pwg_debug_read: utterance out of range");
     pk_ctx* ctx = h->ctx;
@@ -2675,5 +2713,6 @@ extern "C" void pk_pwg_destroy(pk_pwg* h) {
     for (auto* b : bufs) b->release();
     if (h->host_sample) (void)hipHostFree(h->host_sample);
     if (h->ev_sample) (void)hipEventDestroy(h->ev_sample);
+    pwg_gen_destroy(h->gen);
     delete h;
 }

@@ -5,6 +5,11 @@ Mirrors parakeet/models/parallel_wavegan/parallel_wavegan.py:
 ``remove_weight_norm`` :485-496, ``inference`` :498-520) and ``PWGInference``
 (:766-775).  All arithmetic runs in libpk_synth.so (csrc/pwg.hip).
 
+Shapes: the default (in/out 1, kernel 3, residual 64, gate 128, skip 64, aux 80) runs the tuned kernels; every other
+configuration inside the generic envelope runs the shape-generic kernels (csrc/pwg_gen.hip): in/out 1, odd
+kernel_size 1 ... 9, residual and skip channels multiples of 16 in 16 ... 256, gate channels 32 ... 512 with
+gate_channels / 2 a multiple of 16, aux channels 1 ... 512.  Anything else raises NotImplementedError.
+
 Extensions over the reference (superset, not a break): ``inference`` takes an
 optional ``noise=`` (the reference draws ``paddle.randn`` inside the call, which
 cannot be reproduced), and ``inference_batch`` synthesises a ragged batch in
@@ -41,6 +46,9 @@ class PWGGenerator:
         self.layers = layers
         self.stacks = stacks
         self.kernel_size = kernel_size
+        self.residual_channels = residual_channels
+        self.gate_channels = gate_channels
+        self.skip_channels = skip_channels
         self.upsample_factor = int(np.prod(upsample_scales))
         self.training = True
         self._ctx = Context.get(device)
@@ -87,8 +95,11 @@ class PWGGenerator:
         _capi.check(self._ctx.lib.pk_pwg_set_math(self._h, m))
 
     def set_option(self, key, value):
-        """Named integer options of the engine handle (include/pk_synth.h, pk_pwg_set_option): 'planes', 'scale_guard'."""
+        """Named integer options of the engine handle (include/pk_synth.h, pk_pwg_set_option): 'planes', 'scale_guard',
+        'generic_kernel' (1: the default shape on the shape-generic kernels too; applies from the next synthesis), ..."""
         _capi.check(self._ctx.lib.pk_pwg_set_option(self._h, key.encode(), int(value)))
+        if key == "generic_kernel":
+            self._finalized = False
 
     def scale_overshoot(self):
         """(log2(a-priori bound / measured max|x|) per layer input [layers + 1], fell_back) of the last guarded inference
@@ -205,7 +216,7 @@ class PWGGenerator:
         if what == 3:       # max|x| per 32-sample block of the final residual stream (block-scaled split path)
             out = np.empty(((n + 31) // 32,), dtype=np.float32)
         else:
-            rows = {0: 128, 1: 64, 2: 64}[what]
+            rows = {0: self.gate_channels, 1: self.residual_channels, 2: self.skip_channels}[what]
             out = np.empty((rows, n), dtype=np.float32)
         _capi.check(self._ctx.lib.pk_pwg_debug_read(self._h, what, b, _capi.fptr(out), out.size))
         return out

@@ -38,6 +38,24 @@ PWG_LJSPEECH = dict(
     residual_channels=64, gate_channels=128, skip_channels=64, aux_channels=80,
     aux_context_window=2, dropout=0.0, use_weight_norm=True, upsample_scales=[4, 4, 4, 4])
 
+# generator_params of four non-default PWG shapes (tests/golden/pwg_sizes.npz, tools/make_golden_pwg_sizes.py): small, large,
+# another feature set (aux 64, kernel 5, hop 300) and an uneven one; the rest of each config is PWG_LJSPEECH's
+PWG_SIZES = {
+    "A": dict(residual_channels=32, gate_channels=64, skip_channels=32, aux_channels=80, kernel_size=3,
+              layers=10, stacks=2, upsample_scales=[4, 4, 4, 4]),
+    "B": dict(residual_channels=128, gate_channels=256, skip_channels=128, aux_channels=80, kernel_size=3,
+              layers=12, stacks=2, upsample_scales=[4, 4, 4, 4]),
+    "C": dict(residual_channels=64, gate_channels=128, skip_channels=64, aux_channels=64, kernel_size=5,
+              layers=10, stacks=2, upsample_scales=[4, 5, 3, 5]),
+    "D": dict(residual_channels=96, gate_channels=160, skip_channels=32, aux_channels=100, kernel_size=3,
+              layers=6, stacks=3, upsample_scales=[4, 4, 4, 4]),
+}
+
+
+def pwg_size_config(name):
+    return dict(PWG_LJSPEECH, **PWG_SIZES[name])
+
+
 WAVEFLOW_LJSPEECH = dict(upsample_factors=[16, 16], n_flows=8, n_layers=8, n_group=16, channels=128,
                          n_mels=80, kernel_size=[3, 3])   # examples/waveflow/config.py:32-41 (C=64: paper's small model)
 
