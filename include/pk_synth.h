@@ -472,7 +472,25 @@ int pk_tts_set_style_reference(pk_tts* h, const float* speech, const int32_t* le
  * flags: PK_TTS_KEEP_ATT keeps the encoder-decoder attention weights for pk_tts_read. */
 int pk_tts_infer(pk_tts* h, const int64_t* ids, const int32_t* tok_lens, int32_t B, double threshold,
                  double minlenratio, double maxlenratio, const uint64_t* seeds, int32_t flags, int32_t* out_frames);
-/* Postnet + outputs of the last pk_tts_infer (:644-651).
+/* TransformerTTS.inference(..., use_teacher_forcing=True) (:567-579 -> _forward :462-500) for a packed batch, up to (not
+ * including) the postnet.  <eos> is appended as in pk_tts_infer; the style embedding of a use_gst model comes from the
+ * teacher spectrogram itself (self.gst(ys), :475-477); the decoder inputs are ys[:, r - 1::r] with a zero frame in front and
+ * the last row dropped (:484-492), and the whole decoder runs as one pass under the causal target mask (:692-723).  Prenet
+ * dropout stays on: the prenet sees the L_b / r rows of an utterance in one call, the dropout-stream elements of the AR
+ * decode's call at step s = L_b / r.
+ *   ids, tok_lens, seeds  as pk_tts_infer
+ *   speech       float32 packed (sum(L_b), odim) teacher spectrograms in the model's normalised space: device memory, or
+ *                host memory under PK_HOST_IO (a use_gst model copies device speech to the host for its style encoder)
+ *   speech_lens  HOST (B) frames L_b >= reduction_factor
+ *   out_frames   (B) host: (L_b / reduction_factor) * reduction_factor (known up front: no device sync)
+ * Consumes the pending pk_tts_set_speakers rows (required by a model with spk_embed_dim) and drops a pending
+ * pk_tts_set_style_reference.  pk_tts_read (probabilities: the stop head on the teacher-forced rows, an engine extra; the
+ * reference returns None) and pk_tts_debug_read then serve its result.  Refused: more tokens than the AR decode's
+ * attention kernels hold (PK_EUNSUPPORTED), L_b < reduction_factor (PK_EINVAL).
+ * flags: PK_TTS_KEEP_ATT keeps the encoder-decoder attention weights, PK_HOST_IO for `speech`. */
+int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_lens, int32_t B, const float* speech,
+                   const int32_t* speech_lens, const uint64_t* seeds, int32_t flags, int32_t* out_frames);
+/* Postnet + outputs of the last pk_tts_infer or pk_tts_teacher (:644-651).
  *   mel_out   packed (sum(L_b), odim): outs + postnet(outs), de-normalised under PK_APPLY_NORMALIZER
  *   probs_out packed (sum(L_b)) stop probabilities, or NULL
  *   att_out   per utterance (dlayers, aheads, L_b / reduction_factor, T_b) encoder-decoder attention weights (one row

@@ -172,6 +172,7 @@ def _declare(lib):
         "pk_tts_finalize": (C.c_int, [vp]),
         "pk_tts_infer": (C.c_int, [vp, i64p, i32p, i32, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_uint64), i32,
                                    i32p]),
+        "pk_tts_teacher": (C.c_int, [vp, i64p, i32p, i32, f32p, i32p, C.POINTER(C.c_uint64), i32, i32p]),
         "pk_tts_read": (C.c_int, [vp, f32p, f32p, f32p, i32]),
         "pk_tts_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_tts_destroy": (None, [vp]),

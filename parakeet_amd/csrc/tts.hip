@@ -42,6 +42,7 @@
 #include "pk_fft.h"
 #include "pk_gst.h"
 #include "pk_rowgemm.h"
+#include "pk_tts_teacher.h"
 
 namespace {
 
@@ -500,6 +501,7 @@ struct DecLayer {
     Dense qkv, out, src_q, src_kv, src_out, ffn1, ffn2;
     RowW r_qkv, r_out, r_src_q, r_src_out, r_ffn1, r_ffn2;
     RowW r_cat1_x, r_cat1_a, r_cat2_x, r_cat2_a;   // concat_linear1 / 2 (decoder_layer.py:66-68): input half (+ bias), attention half
+    Dense cat1_x, cat1_a, cat2_x, cat2_a;          // ... the same as tile-GEMM layers (pk_tts_teacher)
 };
 }  // namespace
 
@@ -562,6 +564,9 @@ struct pk_tts : pk_fft_core {
     pk_dbuf d_tok, d_e1, d_e2, d_tpe, d_hs, d_valid, d_y, d_p0, d_p1, d_x0, d_t, d_ham, d_pam, d_peb, d_rt, d_rc, d_rx, d_rq,
         d_rf, d_rz, d_ra, d_rn, d_probs, d_state, d_seeds, d_att, d_attoff, d_before, d_q1, d_q2, d_rowmap, d_stage, d_stage2;
     std::vector<pk_dbuf> d_qkv_l, d_xc_l, d_mkv_l;
+    // pk_tts_teacher: the decoder on a timeline of its input rows
+    Timeline tl_dec;
+    pk_dbuf d_tsp, d_tspoff, d_tin, d_tp0, d_tp1, d_tpeb, d_tx, d_tn, d_tham, d_tqkv, d_tsq, d_tc, d_ta, d_tf, d_tout, d_tamax;
 };
 
 // ---------------------------------------------------------------------------------------------- create / params
@@ -813,6 +818,16 @@ int add_qkv(pk_fft_arena& ar, const pk_param_map& P, const std::string& p, int A
     r.N = 3 * A;
     return pk_fft_add_dense_kn(ar, kn, &bias, A, 1, 3 * A, d);
 }
+
+// concat_linear{1,2} as two tile-GEMM layers: x . W[:A] + b and att . W[A:]
+int add_dense_concat(pk_fft_arena& ar, const pk_param_map& P, const std::string& base, int A, Dense& dx, Dense& da) {
+    std::vector<float> w, b;
+    PK_TRY(pk_get_weight(P, base, {2 * A, A}, w));
+    PK_TRY(pk_get_vector(P, base + ".bias", A, b));
+    std::vector<float> wx(w.begin(), w.begin() + (size_t)A * A), wa(w.begin() + (size_t)A * A, w.end());
+    PK_TRY(pk_fft_add_dense_kn(ar, wx, &b, A, 1, A, dx));
+    return pk_fft_add_dense_kn(ar, wa, nullptr, A, 1, A, da);
+}
 }  // namespace
 
 extern "C" int pk_tts_finalize(pk_tts* h) {
@@ -931,6 +946,8 @@ extern "C" int pk_tts_finalize(pk_tts* h) {
         if (c.decoder_concat_after) {
             PK_TRY(add_row_concat(ar, P, p + ".concat_linear1", A, L.r_cat1_x, L.r_cat1_a));
             PK_TRY(add_row_concat(ar, P, p + ".concat_linear2", A, L.r_cat2_x, L.r_cat2_a));
+            PK_TRY(add_dense_concat(ar, P, p + ".concat_linear1", A, L.cat1_x, L.cat1_a));
+            PK_TRY(add_dense_concat(ar, P, p + ".concat_linear2", A, L.cat2_x, L.cat2_a));
         }
     }
     PK_TRY(add_kv(ar, P, "decoder.decoders.0.self_attn", A, h->kv0));
@@ -1622,9 +1639,253 @@ extern "C" int pk_tts_infer(pk_tts* h, const int64_t* ids, const int32_t* tok_le
     return PK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- teacher forcing
+// TransformerTTS.inference(..., use_teacher_forcing=True) (:567-579 -> _forward :462-500): every decoder input row is known, so
+// the decoder runs as ONE pass over a row timeline of the L_b / r input rows of every utterance (tts_teacher.hip).  The
+// results land where pk_tts_infer leaves its own (position-major step rows), so pk_tts_read and pk_tts_debug_read serve both.
+namespace {
+// the widest encoder-decoder attention the AR decode's step kernels hold (attn_step): the teacher call refuses what
+// pk_tts_infer would, so that both calls of one handle accept the same texts
+bool tts_keys_fit(int dk, int n) {
+    if (dk == 64 && n <= 640) return true;
+    return (size_t)(dk + 1032 + n + 4) * sizeof(float) <= 60 * 1024;
+}
+}  // namespace
+
+extern "C" int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_lens, int32_t B, const float* speech,
+                              const int32_t* speech_lens, const uint64_t* seeds, int32_t flags, int32_t* out_frames) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_tts_teacher: NULL argument");
+    // the per-call conditioning is consumed by this call; a pending style reference is dropped (the style comes from `speech`)
+    std::vector<float> spembs;
+    spembs.swap(h->cond_emb);
+    const int condB = h->cond_B;
+    h->cond_B = 0;
+    h->cond_speech.clear();
+    h->cond_speech_lens.clear();
+    if (!ids || !tok_lens || !speech || !speech_lens || !out_frames) PK_FAIL(PK_EINVAL, "pk_tts_teacher: NULL argument");
+    if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_tts_teacher: call pk_tts_finalize first");
+    if (B <= 0) PK_FAIL(PK_EINVAL, "pk_tts_teacher: batch size must be positive");
+    if (h->cfg.spk_embed_dim > 0 && condB != B)
+        PK_FAIL(PK_EINVAL, "pk_tts_teacher: the model integrates a speaker embedding into the encoder output (:480-481): "
+                           "pk_tts_set_speakers needs %d rows, got %d", B, condB);
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const pk_tts_cfg& c = h->cfg;
+    const int A = c.adim, H = c.aheads, dk = A / H, O = c.odim, J = c.dprenet_layers, U = J > 0 ? c.dprenet_units : 16;
+    const int RF = c.reduction_factor, OR = O * RF;
+    const bool post = !c.decoder_normalize_before, cat = c.decoder_concat_after != 0;
+    std::vector<int> Lin(B);
+    std::vector<long> spoff(B);
+    int maxT = 0, maxLin = 0;
+    long total_frames = 0;
+    for (int b = 0; b < B; ++b) {
+        if (tok_lens[b] < 0) PK_FAIL(PK_EINVAL, "pk_tts_teacher: utterance %d has %d tokens", b, tok_lens[b]);
+        if (!tts_keys_fit(dk, tok_lens[b] + 1))
+            PK_FAIL(PK_EUNSUPPORTED, "pk_tts_teacher: utterance %d has %d tokens + <eos>, more than the attention kernels hold", b,
+                    tok_lens[b]);
+        if (speech_lens[b] < RF)
+            PK_FAIL(PK_EINVAL, "pk_tts_teacher: utterance %d has %d teacher frames, fewer than reduction_factor %d", b,
+                    speech_lens[b], RF);
+        Lin[b] = speech_lens[b] / RF;   // ys[:, r - 1::r] (:484-489)
+        spoff[b] = total_frames;
+        total_frames += speech_lens[b];
+        maxT = std::max(maxT, tok_lens[b] + 1);
+        maxLin = std::max(maxLin, Lin[b]);
+    }
+    const long rowsPM = (long)(maxLin + 1) * B;   // position-major rows of pk_tts_read's layout
+    if (rowsPM + SLACK > 0x3fffffff || total_frames > 0x3fffffff) PK_FAIL(PK_EUNSUPPORTED, "pk_tts_teacher: %ld decoder rows", rowsPM);
+    const bool host = (flags & PK_HOST_IO) != 0;
+    // the style reference of a use_gst model is the teacher spectrogram itself (self.gst(ys), :475-477); the style encoder
+    // reads host memory
+    std::vector<float> gst_speech;
+    std::vector<int> gst_lens;
+    if (c.use_gst) {
+        gst_lens.assign(speech_lens, speech_lens + B);
+        if (host) {
+            gst_speech.assign(speech, speech + (size_t)total_frames * O);
+        } else {
+            gst_speech.resize((size_t)total_frames * O);
+            PK_HIP(hipMemcpyAsync(gst_speech.data(), speech, gst_speech.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            PK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    h->inferred = false;
+    h->B = B;
+    h->keep_att = (flags & PK_TTS_KEEP_ATT) != 0;
+    h->T.resize(B);
+    for (int b = 0; b < B; ++b) h->T[b] = tok_lens[b] + 1;
+    PK_TRY(pk_fft_ensure_pe(h, std::max(maxT, maxLin)));
+    PK_TRY(encode(h, ids, tok_lens, B, spembs, gst_speech, gst_lens));
+    const Timeline& tlk = h->tl_tok;
+    PK_TRY(pk_fft_build_timeline(ctx, h->tl_dec, Lin.data(), B, h->gapr));
+    const Timeline& tl = h->tl_dec;
+    const int rows = tl.rows;
+    const int* rutt = tl.d_row_utt();
+    // ---- buffers
+    const float* d_sp = speech;
+    if (host) {
+        PK_TRY(pk_upload(ctx, h->d_tsp, speech, (size_t)total_frames * O * sizeof(float)));
+        d_sp = h->d_tsp.as<float>();
+    }
+    PK_TRY(pk_upload(ctx, h->d_tspoff, spoff.data(), (size_t)B * sizeof(long)));
+    pk_dbuf* rb[] = {&h->d_tin, &h->d_tp0, &h->d_tp1, &h->d_tpeb, &h->d_tx, &h->d_tn, &h->d_tqkv, &h->d_tsq, &h->d_tc, &h->d_ta,
+                     &h->d_tf, &h->d_tout, &h->d_tham};
+    const int rbw[] = {O, U, U, A, A, A, 3 * A, A, A, A, c.dunits, OR, 1};
+    for (int i = 0; i < 13; ++i) PK_TRY(pk_fft_act_reserve(*rb[i], rows, rbw[i]));
+    float* tin = pk_fft_act_ptr(h->d_tin, O);
+    float* tpeb = pk_fft_act_ptr(h->d_tpeb, A);
+    float* x = pk_fft_act_ptr(h->d_tx, A);
+    float* tn = pk_fft_act_ptr(h->d_tn, A);
+    float* ham = pk_fft_act_ptr(h->d_tham, 1);
+    float* qkv = pk_fft_act_ptr(h->d_tqkv, 3 * A);
+    float* tsq = pk_fft_act_ptr(h->d_tsq, A);
+    float* tc = pk_fft_act_ptr(h->d_tc, A);
+    float* ta = pk_fft_act_ptr(h->d_ta, A);
+    float* tf = pk_fft_act_ptr(h->d_tf, c.dunits);
+    float* tout = pk_fft_act_ptr(h->d_tout, OR);
+    PK_TRY(h->d_tamax.reserve((size_t)2 * B * H * 3 * sizeof(unsigned)));
+    unsigned* amax_self = h->d_tamax.as<unsigned>();
+    unsigned* amax_src = amax_self + (size_t)B * H * 3;
+    PK_TRY(rows_reserve(h->d_y, rowsPM, OR));
+    PK_TRY(rows_reserve(h->d_xc_l[c.dlayers - 1], rowsPM, A));
+    PK_TRY(h->d_probs.reserve((size_t)rowsPM * RF * sizeof(float)));
+    const unsigned long long* d_seeds = nullptr;
+    if (seeds) {
+        PK_TRY(pk_upload(ctx, h->d_seeds, seeds, (size_t)B * sizeof(uint64_t)));
+        d_seeds = h->d_seeds.as<unsigned long long>();
+    }
+    h->cap = Lin;
+    h->len = Lin;
+    h->att_off.assign(B, 0);
+    h->att_total = 0;
+    float* att = nullptr;
+    const long* d_attoff = nullptr;
+    if (h->keep_att) {
+        for (int b = 0; b < B; ++b) {
+            h->att_off[b] = h->att_total;
+            h->att_total += (long)c.dlayers * H * Lin[b] * h->T[b];
+        }
+        PK_TRY(h->d_att.reserve((size_t)h->att_total * sizeof(float)));
+        PK_TRY(pk_upload(ctx, h->d_attoff, h->att_off.data(), (size_t)B * sizeof(long)));
+        att = h->d_att.as<float>();
+        d_attoff = h->d_attoff.as<long>();
+    }
+    const bool h3 = h->math == PK_GEMM_MATH_F16X3;
+    auto dense = [&](const char* name, const Dense& d, const float* in, int ldin, float* out, int ldo, int act, const float* res,
+                     int ldr, const float* in_amax) -> int {
+        return pk_fft_run_dense(h, name, d, in, ldin, out, ldo, rows, act, res, ldr, rutt, in_amax);
+    };
+    auto lnorm = [&](const float* in, size_t g, size_t bb, float* out, float* am) -> int {
+        return pk_fft_layernorm_rows(h, in, g, bb, rutt, rows, A, out, am);
+    };
+    // ---- decoder.embed on all input rows (decoder.py:124-127; prenet dropout as the AR decode's call at step s = L_in)
+    PK_TRY(pk_tt_ys_in(ctx, d_sp, h->d_tspoff.as<long>(), O, RF, rutt, tl.d_row_pos(), rows, tin));
+    PK_LAUNCH(ctx, "tts_teacher_pe", k_tts_pe_timeline, dim3(rows), dim3(128), 0, h->d_pe.as<float>(), h->alpha_dec, rutt,
+              tl.d_row_pos(), A, tpeb);
+    const unsigned thr = h->dropout ? pk_dropout_threshold(0.5) : 0u;   // F.dropout's default p (decoder.py:80)
+    const float* in = tin;
+    int ldin = O;
+    for (int j = 0; j < J; ++j) {
+        float* o = pk_fft_act_ptr(j & 1 ? h->d_tp1 : h->d_tp0, U);
+        PK_TRY(dense("tts_teacher_gemm_prenet", h->dprenet[j], in, ldin, o, U, PK_ACT_RELU, nullptr, 0, nullptr));
+        if (h->dropout) PK_TRY(pk_tt_dropout(ctx, o, U, rows, U, rutt, tl.d_row_pos(), tl.d_seg_len(), J, j, d_seeds, thr, 2.0f));
+        in = o;
+        ldin = U;
+    }
+    if (J > 0) {
+        PK_TRY(dense("tts_teacher_gemm_embed", h->dlin, in, ldin, x, A, PK_ACT_NONE, tpeb, A, nullptr));
+    } else {
+        PK_TRY(dense("tts_teacher_gemm_embed", h->dlin, in, ldin, x, A, PK_ACT_NONE, nullptr, 0, nullptr));
+        PK_TRY(lnorm(x, h->dlin_ln_g, h->dlin_ln_b, tn, nullptr));
+        const long n4 = (long)rows * (A / 4);
+        PK_LAUNCH(ctx, "tts_teacher_relu_pe", k_tts_relu_add, dim3(pk_div_up(n4, 256)), dim3(256), 0,
+                  reinterpret_cast<const float4*>(tn), reinterpret_cast<const float4*>(tpeb), n4, reinterpret_cast<float4*>(x));
+    }
+    // ---- decoder layers (decoder_layer.py:74-158 without a cache): x is the residual stream; post-norm blocks sum into tn and
+    // normalise back into x
+    const float att_scale = (float)(1.0 / std::sqrt((double)dk));
+    float* dst = post ? tn : x;
+    for (int l = 0; l < c.dlayers; ++l) {
+        const DecLayer& L = h->dec[l];
+        const float* mkv = pk_fft_act_ptr(h->d_mkv_l[l], 2 * A);
+        if (h3) PK_HIP(hipMemsetAsync(amax_self, 0, (size_t)2 * B * H * 3 * sizeof(unsigned), ctx->stream));
+        // self-attention under the causal target mask (:692-723)
+        const float* t1 = x;
+        if (!post) {
+            PK_TRY(lnorm(x, L.ln1_g, L.ln1_b, tn, h3 ? ham : nullptr));
+            t1 = tn;
+        }
+        PK_TRY(dense("tts_teacher_gemm_qkv", L.qkv, t1, A, qkv, 3 * A, PK_ACT_NONE, nullptr, 0, !post && h3 ? ham : nullptr));
+        if (h3) PK_TRY(pk_tt_amax(ctx, qkv, 3 * A, tl.d_seg_start(), tl.d_seg_len(), B, H, dk, 3, A, 0, maxLin, amax_self));
+        pk_tt_attn a;
+        a.q = qkv; a.ldq = 3 * A; a.k = qkv + A; a.v = qkv + 2 * A; a.ldkv = 3 * A;
+        a.q_start = a.k_start = tl.d_seg_start(); a.q_len = a.k_len = tl.d_seg_len();
+        a.causal = 1; a.scale = att_scale; a.amax = h3 ? amax_self : nullptr; a.out = tc; a.ldo = A; a.heads = H; a.layer = l;
+        PK_TRY(pk_tt_attention(ctx, a, dk, h->math, B, maxLin));
+        if (cat) {
+            PK_TRY(dense("tts_teacher_gemm_attn_out", L.out, tc, A, ta, A, PK_ACT_NONE, nullptr, 0, nullptr));
+            PK_TRY(dense("tts_teacher_gemm_concat1", L.cat1_x, t1, A, dst, A, PK_ACT_NONE, x, A, nullptr));
+            PK_TRY(dense("tts_teacher_gemm_concat1", L.cat1_a, ta, A, dst, A, PK_ACT_NONE, dst, A, nullptr));
+        } else {
+            PK_TRY(dense("tts_teacher_gemm_attn_out", L.out, tc, A, dst, A, PK_ACT_NONE, x, A, nullptr));
+        }
+        if (post) PK_TRY(lnorm(tn, L.ln1_g, L.ln1_b, x, nullptr));
+        // encoder-decoder attention over the utterance's T_b + 1 encoder rows
+        const float* t2 = x;
+        if (!post) {
+            PK_TRY(lnorm(x, L.ln2_g, L.ln2_b, tn, h3 ? ham : nullptr));
+            t2 = tn;
+        }
+        PK_TRY(dense("tts_teacher_gemm_src_q", L.src_q, t2, A, tsq, A, PK_ACT_NONE, nullptr, 0, !post && h3 ? ham : nullptr));
+        if (h3) {
+            PK_TRY(pk_tt_amax(ctx, tsq, A, tl.d_seg_start(), tl.d_seg_len(), B, H, dk, 1, A, 0, maxLin, amax_src));
+            PK_TRY(pk_tt_amax(ctx, mkv, 2 * A, tlk.d_seg_start(), tlk.d_seg_len(), B, H, dk, 2, A, 1, maxT, amax_src));
+        }
+        pk_tt_attn a2;
+        a2.q = tsq; a2.ldq = A; a2.k = mkv; a2.v = mkv + A; a2.ldkv = 2 * A;
+        a2.q_start = tl.d_seg_start(); a2.q_len = tl.d_seg_len(); a2.k_start = tlk.d_seg_start(); a2.k_len = tlk.d_seg_len();
+        a2.causal = 0; a2.scale = att_scale; a2.amax = h3 ? amax_src : nullptr; a2.out = tc; a2.ldo = A; a2.heads = H; a2.layer = l;
+        a2.att = att; a2.att_off = d_attoff;
+        PK_TRY(pk_tt_attention(ctx, a2, dk, h->math, B, maxLin));
+        if (cat) {
+            PK_TRY(dense("tts_teacher_gemm_src_out", L.src_out, tc, A, ta, A, PK_ACT_NONE, nullptr, 0, nullptr));
+            PK_TRY(dense("tts_teacher_gemm_concat2", L.cat2_x, t2, A, dst, A, PK_ACT_NONE, x, A, nullptr));
+            PK_TRY(dense("tts_teacher_gemm_concat2", L.cat2_a, ta, A, dst, A, PK_ACT_NONE, dst, A, nullptr));
+        } else {
+            PK_TRY(dense("tts_teacher_gemm_src_out", L.src_out, tc, A, dst, A, PK_ACT_NONE, x, A, nullptr));
+        }
+        if (post) PK_TRY(lnorm(tn, L.ln2_g, L.ln2_b, x, nullptr));
+        // feed-forward
+        const float* t3 = x;
+        if (!post) {
+            PK_TRY(lnorm(x, L.ln3_g, L.ln3_b, tn, h3 ? ham : nullptr));
+            t3 = tn;
+        }
+        PK_TRY(dense("tts_teacher_gemm_ffn1", L.ffn1, t3, A, tf, c.dunits, PK_ACT_RELU, nullptr, 0, !post && h3 ? ham : nullptr));
+        PK_TRY(dense("tts_teacher_gemm_ffn2", L.ffn2, tf, c.dunits, dst, A, PK_ACT_NONE, x, A, nullptr));
+        if (post) PK_TRY(lnorm(tn, L.ln3_g, L.ln3_b, x, nullptr));
+    }
+    // ---- after_norm, feat_out, prob_out (decoder.py:192-193, :496-500) into the AR decode's layout
+    const int* rpos = tl.d_row_pos();
+    PK_TRY(pk_tt_scatter(ctx, x, A, rutt, rpos, rows, B, 0, pk_fft_act_ptr(h->d_xc_l[c.dlayers - 1], A)));
+    const float* z = x;
+    if (!post) {
+        PK_TRY(lnorm(x, h->dec_after_g, h->dec_after_b, tn, h3 ? ham : nullptr));
+        z = tn;
+    }
+    PK_TRY(dense("tts_teacher_gemm_feat_out", h->feat_out, z, A, tout, OR, PK_ACT_NONE, nullptr, 0, !post && h3 ? ham : nullptr));
+    PK_TRY(pk_tt_scatter(ctx, tout, OR, rutt, rpos, rows, B, 1, pk_fft_act_ptr(h->d_y, OR)));
+    PK_TRY(pk_tt_probs(ctx, z, A, h->W(h->prob_w), h->W(h->prob_bv), RF, rutt, rpos, rows, B, h->d_probs.as<float>()));
+    h->steps = maxLin;
+    h->frames.resize(B);
+    for (int b = 0; b < B; ++b) out_frames[b] = h->frames[b] = Lin[b] * RF;
+    h->inferred = true;
+    return PK_OK;
+}
+
 extern "C" int pk_tts_read(pk_tts* h, float* mel_out, float* probs_out, float* att_out, int32_t flags) {
     if (!h || !mel_out) PK_FAIL(PK_EINVAL, "pk_tts_read: NULL argument");
-    if (!h->inferred) PK_FAIL(PK_ESTATE, "pk_tts_read: call pk_tts_infer first");
+    if (!h->inferred) PK_FAIL(PK_ESTATE, "pk_tts_read: call pk_tts_infer or pk_tts_teacher first");
     if (att_out && !h->keep_att) PK_FAIL(PK_ESTATE, "pk_tts_read: attention weights need PK_TTS_KEEP_ATT at pk_tts_infer");
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
@@ -1754,6 +2015,12 @@ extern "C" void pk_tts_destroy(pk_tts* h) {
     }
     for (auto& b : h->d_xc_l) b.release();
     for (auto& b : h->d_mkv_l) b.release();
+    {
+        pk_dbuf* bt[] = {&h->d_tsp, &h->d_tspoff, &h->d_tin, &h->d_tp0, &h->d_tp1, &h->d_tpeb, &h->d_tx, &h->d_tn, &h->d_tham,
+                         &h->d_tqkv, &h->d_tsq, &h->d_tc, &h->d_ta, &h->d_tf, &h->d_tout, &h->d_tamax};
+        for (pk_dbuf* b : bt) b->release();
+        h->tl_dec.release();
+    }
     h->tl_tok.release();
     h->tl_frm.release();
     delete h;

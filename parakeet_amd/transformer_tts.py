@@ -3,13 +3,15 @@
 Mirrors parakeet/models/transformer_tts/transformer_tts.py: ``TransformerTTS`` (constructor kwargs :172-250,
 ``set_state_dict``, ``eval``, ``inference`` :511-647 -> (outs, probs, att_ws)) and ``TransformerTTSInference``
 (:757-767).  All arithmetic runs in libpk_synth.so (csrc/tts.hip on the shared transformer machinery of csrc/fs2.hip).
-Training (``forward`` / loss) and teacher forcing are out of scope.
+Training (``forward`` / loss) is out of scope.  ``inference(..., use_teacher_forcing=True)`` runs the decoder as one
+parallel pass over the teacher spectrogram (csrc/tts_teacher.hip).
 
 The reference's decoder prenet keeps dropout on at inference (modules/tacotron2/decoder.py:78-81), so its output
 depends on Paddle's random generator.  Here the mask comes from the engine's counter-based dropout stream
 (include/pk_synth.h): ``seed=`` selects it, the same seed gives the same spectrogram on any batch composition.
 
-Extensions (supersets): ``inference_batch`` decodes a ragged batch in lockstep; ``seed`` / ``dropout``.
+Extensions (supersets): ``inference_batch`` decodes a ragged batch in lockstep; ``teacher_forced_batch`` teacher-forces
+a ragged batch in one pass; ``seed`` / ``dropout``.
 """
 import ctypes as C
 
@@ -194,12 +196,81 @@ class TransformerTTS:
             o += L
         return outs
 
+    def teacher_forced_batch(self, texts, speech, seeds=None, spembs=None, return_att=True, denormalize=False):
+        """Teacher forcing for a ragged batch (transformer_tts.py:567-579): lists of (T_b,) token ids (without <eos>) and
+        (L_b, odim) teacher spectrograms in the model's normalised space -> list of (outs ((L_b // r) * r, odim),
+        att_ws (dlayers, aheads, L_b // r, T_b + 1) or None) device tensors.  The style embedding of a ``use_gst`` model
+        comes from the teacher spectrogram (:475-477).  ``spembs``: (B, spk_embed_dim) for a model built with
+        ``spk_embed_dim``.  The stop probabilities of the teacher-forced rows are kept as ``last_probs``."""
+        ctx = Context.get(self._ctx.device)
+        self._finalize()
+        ys = [to_numpy_f32(y) for y in speech]
+        if len(ys) != len(texts):
+            raise ValueError("one teacher spectrogram per utterance")
+        for y in ys:
+            if y.ndim != 2 or y.shape[1] != self.odim:
+                raise ValueError(f"teacher spectrogram of shape {tuple(y.shape)}, expected (L, {self.odim})")
+            if y.shape[0] < self.reduction_factor:
+                raise ValueError(f"teacher spectrogram of {y.shape[0]} frames, fewer than reduction_factor "
+                                 f"{self.reduction_factor}")
+        if spembs is not None:
+            e = to_numpy_f32(spembs).reshape(len(texts), -1)
+            if e.shape[1] != (self.spk_embed_dim or 0):
+                raise ValueError(f"spembs has {e.shape[1]} columns, the model was built with spk_embed_dim={self.spk_embed_dim}")
+            _capi.check(ctx.lib.pk_tts_set_speakers(self._h, _capi.fptr(e), e.shape[0]))
+        else:
+            _capi.check(ctx.lib.pk_tts_set_speakers(self._h, None, 0))
+        ids = [_ids(t) for t in texts]
+        B = len(ids)
+        lens = np.array([len(i) for i in ids], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(ids)) if lens.sum() else np.zeros(1, np.int64)
+        ylens = np.array([y.shape[0] for y in ys], dtype=np.int32)
+        flat_y = np.ascontiguousarray(np.concatenate(ys, axis=0))
+        frames = np.zeros(B, dtype=np.int32)
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+            assert sd.size == B, "one dropout seed per utterance"
+        flags = _capi.PK_HOST_IO | (_capi.PK_TTS_KEEP_ATT if return_att else 0)
+        _capi.check(ctx.lib.pk_tts_teacher(self._h, flat.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), B, _capi.fptr(flat_y),
+                                           ylens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), flags,
+                                           frames.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._last_tok, self._last_frames = [int(v) + 1 for v in lens], [int(v) for v in frames]
+        rows = [L // self.reduction_factor for L in self._last_frames]
+        total = int(frames.sum())
+        mel = ctx.empty((total, self.odim))
+        probs = ctx.empty((total,))
+        att = None
+        if return_att:
+            att = ctx.empty((sum(self._dlayers * self._aheads * S * T for S, T in zip(rows, self._last_tok)),))
+        _capi.check(ctx.lib.pk_tts_read(self._h, dptr(mel), dptr(probs), None if att is None else dptr(att),
+                                        _capi.PK_APPLY_NORMALIZER if denormalize else 0))
+        outs, o, oa = [], 0, 0
+        self.last_probs = []
+        for L, S, T in zip(self._last_frames, rows, self._last_tok):
+            a = None
+            if att is not None:
+                n = self._dlayers * self._aheads * S * T
+                a = wrap(att[oa:oa + n].view(self._dlayers, self._aheads, S, T))
+                oa += n
+            outs.append((wrap(mel[o:o + L]), a))
+            self.last_probs.append(wrap(probs[o:o + L]))
+            o += L
+        return outs
+
     def inference(self, text, speech=None, spembs=None, threshold=0.5, minlenratio=0.0, maxlenratio=10.0,
                   use_teacher_forcing=False, seed=0, denormalize=False):
-        """(T,) int64 -> (outs (L, odim), probs (L,), att_ws (#layers, #heads, L, T + 1)); transformer_tts.py:511-647."""
+        """(T,) int64 -> (outs (L, odim), probs (L,), att_ws (#layers, #heads, L, T + 1)); transformer_tts.py:511-647.
+        With ``use_teacher_forcing``: (outs ((L // r) * r, odim), None, att_ws (#layers, #heads, L // r, T + 1)) for the
+        teacher spectrogram ``speech`` (L, odim) (:567-579)."""
         if use_teacher_forcing:
-            raise NotImplementedError("teacher forcing needs the training graph (transformer_tts.py:568-582)")
-        # ``speech`` feeds teacher forcing (refused above) and the style encoder (:552-588); ignored otherwise
+            assert speech is not None, "speech must be provided with teacher forcing."   # :569
+            outs, att = self.teacher_forced_batch([text], [speech], [seed], None if spembs is None else
+                                                  to_numpy_f32(spembs).reshape(1, -1), True, denormalize)[0]
+            return outs, None, att
+        # ``speech`` feeds teacher forcing and the style encoder (:552-588); ignored otherwise
         return self.inference_batch([text], threshold, minlenratio, maxlenratio, [seed], True, denormalize,
                                     None if spembs is None else to_numpy_f32(spembs).reshape(1, -1),
                                     None if (speech is None or not self.use_gst) else [speech])[0]
