@@ -42,13 +42,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "pk_mfma.h"
 #include "pk_split.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 pkh2 __attribute__((ext_vector_type(2)));
 
 namespace {
 // an octet's 1 KB of a block: [plane hi | lo][row 32][8 halves] -- a half wave's operand load of one k-step is 512 contiguous
@@ -65,39 +60,6 @@ struct Args {
     long in_blk, out_blk;   // bytes per block of the input / output planes
 };
 
-__host__ __device__ inline int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// in-register split of 8 values (wf_layer.hip): hi = v_cvt_pkrtz (round toward zero), x - hi exactly by v_fma_mix_f32, lo = fp16_rne(x - hi)
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const pkh2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * p], v[2 * p + 1]);
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        float l0, l1;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hu), "v"(v[2 * p]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hu), "v"(v[2 * p + 1]));
-        hi[2 * p] = (_Float16)h[0];
-        hi[2 * p + 1] = (_Float16)h[1];
-        lo[2 * p] = (_Float16)l0;
-        lo[2 * p + 1] = (_Float16)l1;
-    }
-}
-// the stored pair of an activation: hi = fp16_rne(s x), lo = fp16_rne(s x - hi) (wf_layer.hip)
-__device__ __forceinline__ void store_pair8(const float (&v)[8], float s, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float t = v[e] * s;
-        const _Float16 h = (_Float16)t;
-        hi[e] = h;
-        lo[e] = (_Float16)(t - (float)h);
-    }
-}
-__device__ __forceinline__ int amax_exp(unsigned bits) {
-    const int e = (int)(bits >> 23);
-    return e < PK_EXP_MIN ? PK_EXP_MIN : (e > PK_EXP_MAX ? PK_EXP_MAX : e);
-}
 // the fp16 value 2^-d twice in a register (d >= 0)
 __device__ __forceinline__ unsigned pow2_neg_h2(int d) {
     const float f = __uint_as_float((unsigned)(127 - min(d, 60)) << 23);
@@ -107,8 +69,6 @@ __device__ __forceinline__ f16x8 h8_of(unsigned u) {
     const u32x4 v = {u, u, u, u};
     return __builtin_bit_cast(f16x8, v);
 }
-__device__ __forceinline__ f16x8 ld_h8(const char* p) { return *reinterpret_cast<const f16x8*>(p); }
-__device__ __forceinline__ void st_h8(char* p, f16x8 v) { *reinterpret_cast<f16x8*>(p) = v; }
 
 // NQ accumulator tiles (32 output channels each) per wave, KQ = Cin / 16, EPI 0: bias + ReLU -> planes, 1: += into fp32 rows.
 // Grid: one workgroup per (row group of `active` blocks, column tile); blockIdx -> (row group, column tile) keeps the column

@@ -17,16 +17,11 @@
 #include <type_traits>
 
 #include "pk_gemm.h"
+#include "pk_mfma.h"
 #include "pk_split.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 constexpr int BM = PK_GEMM_BM, BN = PK_GEMM_BN, BK = PK_GEMM_BK;
-
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // Shared epilogue: acc[mt][nt] is the wave's (32*MT)x64 sub-tile (rows m0 + wm*32*MT + mt*32 + mfma_row(r, hi),
 // columns nblk*128 + wn*64 + nt*32 + i).
@@ -230,8 +225,6 @@ __global__ __launch_bounds__(256, 3) void k_gemm(pk_gemm_args a) {
 // packed blob); an activation row is split as 2^kx * a with kx from a_amax[] = max|A[r, :]| over the rows its taps
 // read (and a2_amax[] for the appended operand), supplied by the producer of A or computed by k_row_amax; the
 // accumulators are multiplied by 2^-(kx + kw) before the epilogue.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 pkh2 __attribute__((ext_vector_type(2)));
 constexpr int HBK = PK_GEMM_HBK;           // 32
 constexpr int H_B_BYTES = 2 * 2 * 4 * 64 * 16;   // 16 KB: [ks 2][part 2][nt 4][lane 64] x 16 B
 constexpr int H_DEPTH = 3;                 // slabs in flight between global memory and LDS
@@ -243,22 +236,6 @@ constexpr int H_DEPTH = 3;                 // slabs in flight between global mem
 //                                                the four waves' inner loops is matrix time won)
 //   Bs[buf][ks 2][part 2][nt 4][lane 64] x 16 B  (weights: pre-split at finalize)
 // so the inner loop is ds_read_b128 + MFMA only.
-__device__ __forceinline__ void gemm_split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        // hi = v_cvt_pkrtz (round toward zero, saturating at +-65504); x - hi exactly by v_fma_mix_f32 on the packed
-        // high part; lo = fp16_rne(x - hi): |x - hi - lo| <= 2^-21 |x|
-        const pkh2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * p], v[2 * p + 1]);
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        float l0, l1;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hu), "v"(v[2 * p]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hu), "v"(v[2 * p + 1]));
-        hi[2 * p] = (_Float16)h[0];
-        hi[2 * p + 1] = (_Float16)h[1];
-        lo[2 * p] = (_Float16)l0;
-        lo[2 * p + 1] = (_Float16)l1;
-    }
-}
 
 // max|A[r, 0..C)| for rows r0 <= r < r1 of a row-major matrix (amax is indexed like A: row r -> amax[r], rows
 // before the base are valid memory on both).  LPR lanes share a row (16 for C <= 64, 32 for C <= 128, else 64), so
@@ -283,19 +260,6 @@ __global__ __launch_bounds__(256) void k_row_amax(const float* __restrict__ A, l
     }
     for (int o = lpr >> 1; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if (sub == 0 && r < r1) amax[r] = m;
-}
-
-// split of 2^k * x (x scaled exactly, then as gemm_split8)
-__device__ __forceinline__ void gemm_split8s(const float (&v)[8], float s, f16x8& hi, f16x8& lo) {
-    float t[8];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        f32x2 u = {v[2 * p], v[2 * p + 1]};
-        u *= s;
-        t[2 * p] = u[0];
-        t[2 * p + 1] = u[1];
-    }
-    gemm_split8(t, hi, lo);
 }
 
 // MT = 32-row MFMA tiles per wave along M: 2 -> 128-row workgroup tiles (2 workgroups per CU), 1 -> 64-row tiles
@@ -372,7 +336,7 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void k_gemm_h3(pk_gemm_args a
             const f32x4 v0 = ra[set][2 * g], v1 = ra[set][2 * g + 1];
             const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
             f16x8 fh, fl;
-            gemm_split8s(v, sx, fh, fl);
+            split8s(v, sx, fh, fl);
             Af[buf][a_slot(lgrp + g, 0)] = fh;
             Af[buf][a_slot(lgrp + g, 1)] = fl;
         }

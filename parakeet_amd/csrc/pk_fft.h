@@ -1,7 +1,7 @@
 // pk_fft.h -- the transformer ("FFT block") machinery shared by the models built from
 // parakeet/modules/fastspeech2_transformer/: FastSpeech2 (fs2.hip, encoder and decoder are both `Encoder`
 // stacks, fastspeech2.py:171,251) and TransformerTTS (tts.hip: the same `Encoder` class as its text encoder,
-// transformer_tts.py:278-292).  Definitions live in fs2.hip; the kernels are documented there.
+// transformer_tts.py:278-292).  Definitions live in fft.hip; the kernels are documented there.
 //
 //   row timeline, Dense / FftLayer weight records, the weight arena      
 //   pk_fft_add_*   finalize-time packing of Linear / Conv1D / FFT stacks / the tacotron2-style Postnet
@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "pk_ffn_planes.h"
 #include "pk_gemm.h"
 
 constexpr int PK_FFT_MAX_HEADS = 16;   // (q|k|v, head) magnitude-bound constants are passed to a kernel by value
@@ -151,7 +152,7 @@ int pk_fft_run_stack(pk_fft_core* h, const std::vector<pk_fft_layer>& layers, si
                      const pk_fft_timeline& tl, int units, float* hs_out, bool normalize_before = true);
 // hs[r] += v[utterance of r] for the rows of a timeline that belong to an utterance; v: [B][adim]
 int pk_fft_add_rowvec(pk_fft_core* h, const pk_fft_timeline& tl, const float* d_vec, float* hs);
-// Speaker-embedding integration on the rows of a timeline ("add" / "concat"; hs_proj NULL = "add"); fs2.hip
+// Speaker-embedding integration on the rows of a timeline ("add" / "concat"; hs_proj NULL = "add")
 int pk_fft_run_speaker(pk_fft_core* h, const pk_fft_timeline& tl, const long long* d_spk_id, const float* d_spembs,
                        size_t table, size_t w, size_t bias, const pk_fft_dense* hs_proj, int D, pk_dbuf& d_vec, float* hs,
                        float* tmp);
@@ -160,3 +161,11 @@ int pk_fft_run_speaker(pk_fft_core* h, const pk_fft_timeline& tl, const long lon
 int pk_fft_run_postnet(pk_fft_core* h, const char* name, const std::vector<pk_fft_dense>& postnet, const float* before,
                        int odim, int chans, const pk_fft_timeline& tl, pk_dbuf& q1, pk_dbuf& q2, float* d_out,
                        const int* out_rowmap, const float* cscale, const float* cshift);
+// A planes work buffer (pk_ffn_planes.h) of C channels for a timeline of nblk blocks with its row maxima, margins zeroed;
+// *planes = block 0, *amax = row 0
+int pk_fft_planes_buf(pk_fft_core* h, pk_dbuf& buf, pk_dbuf& am, int nblk, int C, char** planes, unsigned** amax);
+// ffnp_conv256_launch arguments of a dense layer packed for it (pk_fft_add_dense_kn); the caller sets the output
+FfnpConv pk_fft_conv256_args(pk_fft_core* h, const pk_fft_dense& d, int nblk, const int* row_utt, const void* in,
+                             const unsigned* in_amax);
+// the options of an FFT stack, shared by pk_fs2_set_option and pk_tts_set_option (`who` names the caller in errors)
+int pk_fft_set_option(pk_fft_core* h, const char* key, int64_t value, const char* who);

@@ -1,4 +1,5 @@
-// pk_split.h -- block scaling shared by every split-fp16 kernel (pwg.hip, gemm.hip, fs2.hip attention).
+// pk_split.h -- block scaling shared by every split-fp16 kernel (pwg.hip, gemm.hip, the attention kernels of fft.hip, ...);
+// the in-register split itself is pk_mfma.h.
 //
 // A product a*b of fp32 values is evaluated as a_hi*b_hi + a_lo*b_hi + a_hi*b_lo on v_mfma_f32_32x32x16_f16 with
 // x_hi = fp16(x), x_lo = fp16(x - x_hi).  fp16 has 5 exponent bits: x_hi is a full 11-bit part only for

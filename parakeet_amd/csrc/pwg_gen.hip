@@ -34,14 +34,13 @@
 #include <vector>
 
 #include "pk_gemm.h"
+#include "pk_mfma.h"
 #include "pk_split.h"
 #include "pwg_gen.h"
 
 namespace {
 
-typedef float gf32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GT = 64;           // samples per workgroup tile
 constexpr int GUPW = 5;          // frames of the composite upsampler (pwg.hip: UPW)
@@ -53,14 +52,12 @@ constexpr float G_SQRT_HALF = 0.70710678118654752440f;
 
 enum { GM_F32 = 0, GM_F16X3 = 1, GM_BF16X3 = 2 };
 
-__host__ __device__ inline int g_mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-template <int MODE> struct GSplit { typedef gf16x8 vec; typedef _Float16 elem; };
+template <int MODE> struct GSplit { typedef f16x8 vec; typedef _Float16 elem; };
 template <> struct GSplit<GM_BF16X3> { typedef gbf16x8 vec; typedef __bf16 elem; };
-__device__ __forceinline__ gf32x16 g_mfma16(gbf16x8 a, gbf16x8 b, gf32x16 c) {
+__device__ __forceinline__ f32x16 g_mfma16(gbf16x8 a, gbf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ gf32x16 g_mfma16(gf16x8 a, gf16x8 b, gf32x16 c) {
+__device__ __forceinline__ f32x16 g_mfma16(f16x8 a, f16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 // hi = round(v), lo = round(v - hi) (round to nearest even in both formats)
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(256) void k_pwg_block_gen(GenLayer a) {
         const int ts = t0 + 32 * st;
         const int s = ts - toff + n;
         const bool valid = s < S;
-        gf32x16 aa = {}, ab = {};
+        f32x16 aa = {}, ab = {};
         int kx = 0;
         if constexpr (MODE != GM_F32) {   // the x operand's scale: max over the blocks this half tile's taps touch
             unsigned m = 0u;
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(256) void k_pwg_block_gen(GenLayer a) {
         float* zrow = zl + (32 * st + n) * ZMAX;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = 32 * jb + g_mfma_row(r, hi);
+            const int j = 32 * jb + mfma_row(r, hi);
             float z = 0.f;
             if (j < Gh) {
                 float ca = 0.f, cb = 0.f;
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(256) void k_pwg_block_gen(GenLayer a) {
         const int ts = t0 + 32 * st;
         const bool valid = ts - toff + n < S;
         const float* zr = zl + (32 * st + n) * ZMAX;
-        gf32x16 acc = {};
+        f32x16 acc = {};
         float inv = 1.f;
         if constexpr (MODE == GM_F32) {
             const int ks2 = GH / 2;
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(256) void k_pwg_block_gen(GenLayer a) {
         float m = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = 32 * ob + g_mfma_row(r, hi);
+            const int o = 32 * ob + mfma_row(r, hi);
             if (o < R) {
                 const long i = blk * R * 32 + o * 32 + n;
                 const float v = acc[r] * inv + a.bias[a.G + o];
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(256) void k_pwg_last_gen(GenLast a) {
         const int ob = u >> 1, st = u & 1;
         const float* sp = a.skip + (long)((t0 >> 5) + st) * a.SK * 32 + n;
         const float* w = a.w1f + (size_t)ob * ks2 * 64 + lane;
-        gf32x16 acc = {};
+        f32x16 acc = {};
         for (int ks = 0; ks < ks2; ++ks) {
             const float y = fmaxf(sp[(2 * ks + hi) * 32] * a.scale, 0.f);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[(size_t)ks * 64], y, acc, 0, 0, 0);
@@ -335,7 +332,7 @@ __global__ __launch_bounds__(256) void k_pwg_last_gen(GenLast a) {
         float ps = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = 32 * ob + g_mfma_row(r, hi);
+            const int o = 32 * ob + mfma_row(r, hi);
             ps = fmaf(fmaxf(acc[r] + a.b1[o], 0.f), a.w2[o], ps);
         }
         part[2 * ob + hi][32 * st + n] = ps;

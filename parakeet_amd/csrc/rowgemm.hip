@@ -2,6 +2,7 @@
 #include "pk_rowgemm.h"
 
 #include "pk_gemm.h"
+#include "pk_mfma.h"
 #include "pk_philox.h"
 
 void pk_rowgemm_pack(const float* Wkn, int K, int N, std::vector<float>& out) {
@@ -23,9 +24,6 @@ void pk_rowgemm_lstm_perm(int H, std::vector<int>& perm) {
 
 namespace {
 constexpr int KC = PK_RG_KC, ROWS = PK_RG_ROWS;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float rg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // One workgroup = 16 output columns x up to 32 rows, 8 waves; the K range is dealt out in steps of 16 k, wave w takes the steps
 // w, w + 8, ...  Latency is everything here (32 rows: a launch is 10 - 40 MFLOP), and round 4's rocprof / HIP-event figures put
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(512) void k_rowgemm(pk_rowgemm_args a) {
             const int u = blockIdx.x * 4 + jj;
             if (m < rows && u < a.lstm_H) {
                 const float* g = gl + m * CW;
-                const float gi = rg_sigmoid(g[jj]), gf = rg_sigmoid(g[4 + jj]), gg = tanhf(g[8 + jj]), go = rg_sigmoid(g[12 + jj]);
+                const float gi = sigmoidf_(g[jj]), gf = sigmoidf_(g[4 + jj]), gg = tanhf(g[8 + jj]), go = sigmoidf_(g[12 + jj]);
                 float* cp = a.lstm_c + (long)(m0 + m) * a.lstm_H + u;
                 const float cn = gf * *cp + gi * gg;
                 const float h = go * tanhf(cn);

@@ -28,20 +28,15 @@
 #include <vector>
 
 #include "pk_fft.h"
+#include "pk_mfma.h"
 #include "pk_split.h"
 
 namespace {
 typedef pk_fft_dense Dense;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SPK_M = 32;          // partials per workgroup (one MFMA row block)
 constexpr int SPK_WAVES = 8;
 constexpr int SPK_MAX_H = 512;
-
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct RecArgs {
     const float* xg;      // [P * T][4H]: x W_ih^T + b_ih + b_hh, row p * T + t

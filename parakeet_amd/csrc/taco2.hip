@@ -31,13 +31,12 @@
 
 #include "pk_ar.h"
 #include "pk_fft.h"
+#include "pk_mfma.h"
 #include "pk_rowgemm.h"
 
 namespace {
 typedef pk_fft_dense Dense;
 typedef pk_fft_timeline Timeline;
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // x[r] = E[id[r]] + (tone[r] != 0 ? Et[tone[r]] : 0)   (:807-810; embedding_tones has padding_idx 0), gap rows zero
 __global__ __launch_bounds__(128) void k_taco_embed(const int* __restrict__ tok, const int* __restrict__ tone,

@@ -9,7 +9,7 @@
 //   Postnet                    parakeet/modules/tacotron2/decoder.py:127-198
 //
 // The text encoder is the same `Encoder` class FastSpeech2 uses: it runs on the shared row-timeline machinery of
-// pk_fft.h (fs2.hip).  The decoder is autoregressive; what the engine does with the reference's loop:
+// pk_fft.h (fft.hip).  The decoder is autoregressive; what the engine does with the reference's loop:
 //
 //  * B utterances are decoded in lockstep, one frame per step for every utterance.  All per-frame tensors are
 //    POSITION-MAJOR: row = pos * B + b, so the rows of steps 1..s are the contiguous prefix [0, s*B) and every GEMM
@@ -662,7 +662,6 @@ extern "C" int pk_tts_set_math(pk_tts* h, int32_t mode) {
     return PK_OK;
 }
 
-int pk_fft_set_option(pk_fft_core* h, const char* key, int64_t value, const char* who);   // fs2.hip
 extern "C" int pk_tts_set_option(pk_tts* h, const char* key, int64_t value) {
     if (!h || !key) PK_FAIL(PK_EINVAL, "pk_tts_set_option: NULL argument");
     if (strcmp(key, "kv_prefix") == 0) {

@@ -21,26 +21,18 @@
 #include <cmath>
 
 #include "pk_gemm.h"
+#include "pk_mfma.h"
 #include "pk_philox.h"
 #include "pk_split.h"
 #include "pk_tts_teacher.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-typedef _Float16 tt_f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 tt_pkh2 __attribute__((ext_vector_type(2)));
-
-// x = hi + lo: hi = fp16 round toward zero, lo = fp16_rne(x - hi) (the split of fs2.hip's attention kernels)
-__device__ __forceinline__ void tt_split8(const float (&v)[8], tt_f16x8& hi, tt_f16x8& lo) {
+// x = hi + lo: hi = fp16 round toward zero, lo = fp16_rne(x - hi) (plain C here; pk_mfma.h split8 is the same split through v_fma_mix_f32)
+__device__ __forceinline__ void tt_split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const tt_pkh2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * p], v[2 * p + 1]);
+        const pkh2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * p], v[2 * p + 1]);
         const float h0 = (float)h[0], h1 = (float)h[1];
         hi[2 * p] = (_Float16)h[0];
         hi[2 * p + 1] = (_Float16)h[1];
@@ -48,13 +40,13 @@ __device__ __forceinline__ void tt_split8(const float (&v)[8], tt_f16x8& hi, tt_
         lo[2 * p + 1] = (_Float16)(v[2 * p + 1] - h1);
     }
 }
-__device__ __forceinline__ void tt_split8s(const float (&v)[8], float s, tt_f16x8& hi, tt_f16x8& lo) {
+__device__ __forceinline__ void tt_split8s(const float (&v)[8], float s, f16x8& hi, f16x8& lo) {
     float t[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = v[e] * s;
     tt_split8(t, hi, lo);
 }
-__device__ __forceinline__ f32x16 tt_mfma3(tt_f16x8 ah, tt_f16x8 al, tt_f16x8 bh, tt_f16x8 bl, f32x16 c) {
+__device__ __forceinline__ f32x16 tt_mfma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void k_tt_attn_h3(pk_tt_attn a) {
     const float c2 = a.scale * pow2f(-eq) * pow2f(-ek) * 1.4426950408889634f;   // accumulator -> logit in log2 units
     const float co = pow2f(-ev);
 
-    tt_f16x8 qh[KS], ql[KS];
+    f16x8 qh[KS], ql[KS];
     {
         const float* qp = qb + (long)min(q0 + j, nq - 1) * a.ldq + 8 * hi;
 #pragma unroll
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void k_tt_attn_h3(pk_tt_attn a) {
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(kp + 16 * ks);
             const f32x4 v1 = *reinterpret_cast<const f32x4*>(kp + 16 * ks + 4);
             const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            tt_f16x8 kh, kl;
+            f16x8 kh, kl;
             tt_split8s(v, sk, kh, kl);
             S = tt_mfma3(kh, kl, qh[ks], ql[ks], S);
         }
@@ -268,14 +260,14 @@ __global__ __launch_bounds__(256, 1) void k_tt_attn_h3(pk_tt_attn a) {
                 pv[e] = S[8 * s2 + e];
                 voff[e] = (long)min(k0 + mfma_row(8 * s2 + e, hi), nk - 1) * a.ldkv;
             }
-            tt_f16x8 ph, pl;
+            f16x8 ph, pl;
             tt_split8(pv, ph, pl);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 float vv[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) vv[e] = vp[voff[e] + 32 * dt];
-                tt_f16x8 vh, vl;
+                f16x8 vh, vl;
                 tt_split8s(vv, sv, vh, vl);
                 O[dt] = tt_mfma3(vh, vl, ph, pl, O[dt]);   // O^T += V^T P^T
             }

@@ -33,14 +33,8 @@
 #include <type_traits>
 
 #include "pk_grid.h"
+#include "pk_mfma.h"
 #include "pk_split.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 pkh2 __attribute__((ext_vector_type(2)));
 
 #ifndef PK_WF_BIG16
 #define PK_WF_BIG16 1     // the register diet of the 128-channel kernel with fp16 operands too (0: its round-4 form, 8 spilled registers).
@@ -121,53 +115,6 @@ struct Shape {
     static_assert(SLAB2 * KCH2 <= SLAB_CH && CPT2 <= CPT1, "an out-projection slab fits a slab buffer and the staging registers");
 };
 
-__host__ __device__ inline int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// hi = v_cvt_pkrtz (round toward zero, saturating); x - hi exactly by v_fma_mix_f32; lo = fp16_rne(x - hi)
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const pkh2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * p], v[2 * p + 1]);
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        float l0, l1;
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hu), "v"(v[2 * p]));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hu), "v"(v[2 * p + 1]));
-        hi[2 * p] = (_Float16)h[0];
-        hi[2 * p + 1] = (_Float16)h[1];
-        lo[2 * p] = (_Float16)l0;
-        lo[2 * p + 1] = (_Float16)l1;
-    }
-}
-// The stored pair of a layer input (producer side, once per value): hi = fp16_rne(s x), lo = fp16_rne(s x - hi).  Round to
-// nearest, not toward zero as in the in-register splits above: |lo| is at most half an ulp of hi (one more bit for the pair),
-// and hi alone IS the correctly rounded fp16 of the value -- the fp16-operand mode reads only the hi plane.  (The block scale
-// keeps |s x| below 2^14, so the conversion cannot overflow.)
-__device__ __forceinline__ void store_pair8(const float (&v)[8], float s, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float t = v[e] * s;
-        const _Float16 h = (_Float16)t;
-        hi[e] = h;
-        lo[e] = (_Float16)(t - (float)h);
-    }
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_max_step(float v) {
-    const int t = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-    return fmaxf(v, __int_as_float(t));
-}
-__device__ __forceinline__ float wave_max64(float v) {   // wave-uniform maximum (see pwg.hip)
-    v = dpp_max_step<0xB1, 0xf>(v);
-    v = dpp_max_step<0x4E, 0xf>(v);
-    v = dpp_max_step<0x124, 0xf>(v);
-    v = dpp_max_step<0x128, 0xf>(v);
-    v = dpp_max_step<0x142, 0xa>(v);
-    v = dpp_max_step<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 // 2^14 * tanh(a / S) * sigmoid(b / S) from accumulators that hold S * (pre-activation): ca = -2 log2(e) / S, cb = ca / 2
 __device__ __forceinline__ float gated_s(float a, float b, float ca, float cb) {
     const float ta = __builtin_amdgcn_fmed3f(a * ca, -28.853900817779268f, 28.853900817779268f);
@@ -192,11 +139,6 @@ __device__ __forceinline__ f32x2 gated_s2(f32x2 a, f32x2 b, float ca, float cb) 
     rc[1] = __builtin_amdgcn_rcpf(den[1]);
     return num * rc;
 }
-// biased exponent of a block maximum, clamped as blk_scale_exp clamps it (pk_split.h)
-__device__ __forceinline__ int amax_exp(unsigned bits) {
-    const int e = (int)(bits >> 23);
-    return e < PK_EXP_MIN ? PK_EXP_MIN : (e > PK_EXP_MAX ? PK_EXP_MAX : e);
-}
 // eight copies of the fp16 value 2^-d (d >= 0; subnormal / zero beyond 2^-14: what the rescaled values would be anyway)
 __device__ __forceinline__ f16x8 pow2_neg_h8(int d) {
     const float f = __uint_as_float((unsigned)(127 - min(d, 60)) << 23);
@@ -211,8 +153,6 @@ __device__ __forceinline__ float xor32(float v, int lane, bool own_lane) {
 #endif
     return __shfl_xor(v, 32);
 }
-__device__ __forceinline__ f16x8 ld_h8(const char* p) { return *reinterpret_cast<const f16x8*>(p); }
-__device__ __forceinline__ void st_h8(char* p, f16x8 v) { *reinterpret_cast<f16x8*>(p) = v; }
 // Round 6: the 64-channel kernels store the next layer's planes with non-temporal stores -- 21 MB per launch that the kernel
 // boundary then does not have to write back from L2 (one-box A/B, profiles/r06_wf_ab.txt: 64 channels -1.5 % in both maths;
 // 128 channels -0.4 % / +0.6 %: left as plain stores).  PK_WF_NT_STORE=0: plain stores everywhere (the A/B).

@@ -3,7 +3,8 @@
 Mirrors parakeet/models/fastspeech2/fastspeech2.py: ``FastSpeech2`` (constructor
 kwargs :52-118, ``set_state_dict``, ``eval``, ``inference`` :468-558) and
 ``FastSpeech2Inference`` (:662-671).  All arithmetic runs in libpk_synth.so
-(csrc/fs2.hip, csrc/gemm.hip).  Training (``forward`` / loss) is out of scope.
+(csrc/fs2.hip on the transformer machinery of csrc/fft.hip, csrc/gemm.hip).
+Training (``forward`` / loss) is out of scope.
 
 Extension over the reference: ``inference_batch`` runs a ragged batch in one
 engine call (the reference's ``inference`` is one utterance per call).

@@ -2,7 +2,7 @@
 
 Mirrors parakeet/models/transformer_tts/transformer_tts.py: ``TransformerTTS`` (constructor kwargs :172-250,
 ``set_state_dict``, ``eval``, ``inference`` :511-647 -> (outs, probs, att_ws)) and ``TransformerTTSInference``
-(:757-767).  All arithmetic runs in libpk_synth.so (csrc/tts.hip on the shared transformer machinery of csrc/fs2.hip).
+(:757-767).  All arithmetic runs in libpk_synth.so (csrc/tts.hip on the shared transformer machinery of csrc/fft.hip).
 Training (``forward`` / loss) is out of scope.  ``inference(..., use_teacher_forcing=True)`` runs the decoder as one
 parallel pass over the teacher spectrogram (csrc/tts_teacher.hip).
 

@@ -1,7 +1,8 @@
 """Build tools/hipemu/_build/libpk_synth_emu.so: the engine's .hip sources compiled as host C++ against the
 stand-in <hip/hip_runtime.h> of this directory (DEVELOPMENT ONLY -- see that header).
 
-Two source rewrites happen on the way (copies under _build/src, the originals are untouched):
+Three source rewrites happen on the way (copies of the .hip files and of the csrc/ headers under _build/src, which comes
+first on the include path; the originals are untouched):
   * ``extern __shared__ float x[];``  ->  a pointer to the emulator's dynamic-LDS block;
   * the one inline-assembly idiom of the code base (v_fma_mix_f32 d, h[sel], -1.0, x) -> hipemu::fma_mix_sub;
   * a comment line starting with ``// [wave-lds-exchange]`` -> hipemu::wave_sync(): the places where lanes of one wave
@@ -55,7 +56,13 @@ def sources():
 def build(verbose=False, opt="-O1"):
     os.makedirs(os.path.join(OUT, "src"), exist_ok=True)
     flags = [CXX, "-std=c++17", opt, "-g", "-fPIC", "-fno-strict-aliasing", "-Wno-unknown-attributes", "-Wno-unused-value",
-             "-Wno-pass-failed", "-I" + HERE, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+             "-Wno-pass-failed", "-I" + os.path.join(OUT, "src"), "-I" + HERE, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+    for h in os.listdir(CSRC):   # the headers hold device code too (pk_mfma.h: the split): the same rewrites
+        if h.endswith(".h"):
+            with open(os.path.join(CSRC, h)) as f:
+                text = rewrite(f.read())
+            with open(os.path.join(OUT, "src", h), "w") as f:
+                f.write(text)
     jobs = []
     stamp_deps = [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__)]
     stamp_deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
