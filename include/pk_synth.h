@@ -635,6 +635,9 @@ int pk_op_scaled_dot_product_attention(pk_ctx* ctx, const float* q, const float*
 /* Conv1dBatchNorm.forward (conv.py:186-260) in eval mode, data_format "NLC", stride 1, symmetric
  * padding: x (B,T,Cin) device -> y (B, T+2*pad-k+1, Cout) device.  weight [Cout][Cin][k], bias [Cout] or
  * NULL, BatchNorm1D weight/bias/_mean/_variance [Cout] (all four or none) are HOST pointers.
+ * Supported range: 1 <= k <= 12, Cin a multiple of 16 (else PK_EUNSUPPORTED), any pad >= 0 with
+ * T + 2*pad - k + 1 >= 1 (else PK_ESHAPE) -- pad may exceed k - 1, the output is then longer than the input
+ * by rows that see only zeros and hold the folded bias, as with paddle.nn.Conv1D.
  * Synchronous (weights are packed per call). */
 int pk_op_conv1d_batchnorm_nlc(pk_ctx* ctx, const float* x, int32_t B, int32_t T, int32_t Cin,
                                int32_t Cout, int32_t k, int32_t pad, const float* weight,

@@ -3,6 +3,7 @@
 //   scaled_dot_product_attention parakeet/modules/attention.py:22-58 (float mask, returns the weights)
 //   Conv1dBatchNorm.forward      parakeet/modules/conv.py:186-260 (eval mode, NLC layout)
 // Not on the FastSpeech2/PWG/WaveFlow path; they serve the other models' inference code.
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -270,7 +271,11 @@ extern "C" int pk_op_conv1d_batchnorm_nlc(pk_ctx* ctx, const float* x, int32_t B
     }
     pk_conv_to_kn(w.data(), Cout, Cin, k, kn);
     pk_gemm_pack(kn.data(), Cin * k, Cout, packed);
-    const int gap = k;   // >= both paddings
+    // zero rows between sequences: the leading zeros (pad), the trailing zeros (k - 1 - pad where positive) and the
+    // Tout - T = 2*pad - k + 1 extra output rows of a padding above (k-1)/2, so that every output row of a sequence
+    // has a timeline row of its own and every tap of it reads zeros or its own sequence
+    const int gap = std::max(k, std::max(pad, 2 * pad - k + 1));
+    if ((long)gap + (long)B * ((long)T + gap) > (1L << 30)) PK_FAIL(PK_EUNSUPPORTED, "conv1d: row timeline too long");
     const int rows = gap + B * (T + gap);
     const int rows_alloc = ((rows + PK_GEMM_BM - 1) / PK_GEMM_BM) * PK_GEMM_BM + 2 * gap;
     pk_dbuf d_w, d_b, d_tl, d_map;
