@@ -277,6 +277,16 @@ int pk_fs2_set_speakers(pk_fs2* h, const int64_t* spk_id, const float* spembs, i
  * 1-D tone ids of FastSpeech2.inference: hs[t] += tone_projection(normalize(tone_embedding_table[tone[t]]))).
  * tone_id: HOST int64 packed by utterance like the token ids (n = sum of token counts); NULL clears. */
 int pk_fs2_set_tones(pk_fs2* h, const int64_t* tone_id, int64_t n);
+/* Given durations / pitch / energy of the NEXT pk_fs2_encode call: teacher forcing (_forward(..., ds, ps, es,
+ * is_inference=False) :433-442) and prosody control.  HOST arrays packed by utterance like the token ids, n = sum of
+ * token counts (another n -> PK_ESHAPE from that encode); each pointer may be NULL, all NULL clears; a negative duration
+ * -> PK_EINVAL.  A given array stands in for the predictor's value of that quantity only, where it is consumed:
+ * durations feed the prefix sums as they are -- no exp, no rounding, no alpha (length_regulator(hs, ds) :442; alpha
+ * still scales PREDICTED durations) -- and count decoder rows: with reduction_factor r an utterance gets r * sum(d) mel
+ * frames.  The predictors run all the same; with given durations the duration head writes DurationPredictor.forward
+ * (log domain, masked to 0, unrounded; duration_predictor.py:85-103), the d_outs _forward returns in that mode.
+ * The setting is consumed by the encode, whether it succeeds or not. */
+int pk_fs2_set_targets(pk_fs2* h, const int64_t* durations, const float* pitch, const float* energy, int64_t n);
 /* Phase 1 of inference (_forward :390-432): encoder, pitch/energy/duration predictors, prefix
  * sums.  ids: HOST int64, packed by utterance (sum(tok_lens)); tok_lens: HOST (B).
  * alpha = LengthRegulator speed control.  out_frames (HOST, B) receives the number of mel
@@ -287,6 +297,14 @@ int pk_fs2_encode(pk_fs2* h, const int64_t* ids, const int32_t* tok_lens, int32_
  * mel_out: (sum(out_frames), odim) float32 packed by utterance; device pointer, or host with
  * PK_HOST_IO. */
 int pk_fs2_decode(pk_fs2* h, float* mel_out, int32_t flags);
+/* The predictor outputs of the last pk_fs2_encode for the whole batch (d_outs, p_outs, e_outs of _forward :410-433):
+ * HOST arrays of n = sum(tok_lens) floats packed by utterance, each may be NULL.  d_outs: the integer durations of the
+ * inference branch (alpha applied), or the log-domain output when durations were given.  Needs no decode. */
+int pk_fs2_read_predictions(pk_fs2* h, float* d_outs, float* p_outs, float* e_outs, int64_t n);
+/* before_outs of the last pk_fs2_decode (:457, never de-normalised), packed like its mel: (sum(out_frames), odim),
+ * device pointer, or host with PK_HOST_IO.  A model without postnet has no separate tensor (after_outs IS before_outs,
+ * :460-461) -> PK_ESTATE. */
+int pk_fs2_read_before(pk_fs2* h, float* before_out, int32_t flags);
 /* Test taps of the last encode/decode for utterance b, copied to host:
  * 0 hs (T,adim) | 1 pitch (T) | 2 energy (T) | 3 durations (T) | 4 length-regulated hs (L,adim; needs
  * pk_fs2_set_debug(1)) | 5 decoder output (L,adim) | 6 before_outs (L,odim). */
@@ -603,10 +621,17 @@ int pk_mel_create(pk_ctx* ctx, const pk_mel_cfg* cfg, const float* window, const
 int pk_mel_num_frames(pk_mel* h, int32_t n_samples, int32_t* frames);
 /* wav: packed samples, lens (B) host.  out is packed by utterance, time-major:
  * what 0: (frames, 2*n_bin) real | imag (STFT.forward); 1: (frames, n_bin) magnitude / power;
- * 2: (frames, n_mels) mel (then log if configured). */
+ * 2: (frames, n_mels) mel (then log if configured);
+ * 3: (frames, 1) frame energy sqrt(max(sum_k |X_k|^2, log_floor)) (get_feats.py Energy :196-203), reduced in the kernel
+ *    that reads the frame's spectrum. */
 int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int32_t B, float* out,
                int32_t what, int32_t flags);
 void pk_mel_destroy(pk_mel* h);
+/* Token averages of frame-level features (get_feats.py _average_by_duration :141-153, :205-214):
+ * out[t] = mean(x[cum[t-1]:cum[t]]) over the frames of token t, 0 for a token of 0 frames; spans are cut at `frames`
+ * like a numpy slice.  x: DEVICE (frames, C); durations: HOST (T), >= 0; out: DEVICE (T, C).  Synchronises. */
+int pk_op_average_by_duration(pk_ctx* ctx, const float* x, int64_t frames, int32_t C, const int64_t* durations,
+                              int32_t T, float* out);
 
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).

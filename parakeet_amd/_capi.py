@@ -138,6 +138,9 @@ def _declare(lib):
         "pk_fs2_set_option": (C.c_int, [vp, cstr, i64]),
         "pk_fs2_set_speakers": (C.c_int, [vp, i64p, f32p, i32]),
         "pk_fs2_set_tones": (C.c_int, [vp, i64p, i64]),
+        "pk_fs2_set_targets": (C.c_int, [vp, i64p, f32p, f32p, i64]),
+        "pk_fs2_read_predictions": (C.c_int, [vp, f32p, f32p, f32p, i64]),
+        "pk_fs2_read_before": (C.c_int, [vp, f32p, i32]),
         "pk_fs2_finalize": (C.c_int, [vp]),
         "pk_fs2_encode": (C.c_int, [vp, i64p, i32p, i32, C.c_float, i32p]),
         "pk_fs2_decode": (C.c_int, [vp, f32p, i32]),
@@ -196,6 +199,7 @@ def _declare(lib):
         "pk_mel_num_frames": (C.c_int, [vp, i32, i32p]),
         "pk_mel_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32, i32]),
         "pk_mel_destroy": (None, [vp]),
+        "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),
         "pk_op_scaled_dot_product_attention": (C.c_int, [vp, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32,

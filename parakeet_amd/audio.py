@@ -83,7 +83,7 @@ class _Engine:
         ctx = Context.get(self.ctx.device)
         lens = np.array([int(np.prod(w.shape)) for w in wavs], dtype=np.int32)
         x = torch.cat([ctx.to_device(w).reshape(-1) for w in wavs])
-        cols = {0: 2 * self.n_bin, 1: self.n_bin, 2: self.n_mels}[what]
+        cols = {0: 2 * self.n_bin, 1: self.n_bin, 2: self.n_mels, 3: 1}[what]
         nf = [self.frames(n) for n in lens]
         out = ctx.empty((sum(nf), cols))
         _capi.check(ctx.lib.pk_mel_run(self.h, dptr(x), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(wavs),
@@ -180,6 +180,60 @@ class LogMelFBank:
 
     def get_log_mel_fbank_batch(self, wavs, base="10"):
         return [wrap(o) for o in self._engine(base).run(list(wavs), 2)]
+
+
+def average_by_duration_numpy(x, d):
+    """The reference's loop (get_feats.py:205-214; ``Pitch._average_by_duration`` :141-153 is the same plain mean, its
+    mask line changes nothing) as one vectorised host expression: the mean of ``x[cum[t-1]:cum[t]]`` per token, 0 for
+    a token of 0 frames.  (T,) for 1-D ``x``, (T, C) otherwise."""
+    x = np.asarray(x)
+    d = np.asarray(d, dtype=np.int64).reshape(-1)
+    cum = np.minimum(np.concatenate([[0], np.cumsum(d)]), x.shape[0])
+    csum = np.concatenate([np.zeros((1,) + x.shape[1:], np.float64), np.cumsum(x.astype(np.float64), axis=0)], axis=0)
+    n = (cum[1:] - cum[:-1]).reshape((-1,) + (1,) * (x.ndim - 1))
+    tot = csum[cum[1:]] - csum[cum[:-1]]
+    return np.where(n > 0, tot / np.maximum(n, 1), 0.0).astype(x.dtype if x.dtype.kind == "f" else np.float64)
+
+
+def average_by_duration(x, d):
+    """Token averages of a frame-level feature on the engine (``pk_op_average_by_duration``): ``x`` (frames,) or
+    (frames, C), ``d`` (T,) integer durations -> device tensor (T,) / (T, C); 0 for a token of 0 frames."""
+    ctx = Context.get()
+    xt = ctx.to_device(x)
+    one_d = xt.dim() == 1
+    xt = xt.reshape(xt.shape[0], -1)
+    dur = np.ascontiguousarray(np.asarray(d.cpu() if isinstance(d, torch.Tensor) else d).astype(np.int64).reshape(-1))
+    out = ctx.empty((dur.size, xt.shape[1]))
+    if dur.size:
+        _capi.check(ctx.lib.pk_op_average_by_duration(ctx.handle, dptr(xt), xt.shape[0], xt.shape[1],
+                                                      dur.ctypes.data_as(C.POINTER(C.c_int64)), dur.size, dptr(out)))
+    return wrap(out[:, 0] if one_d else out)
+
+
+class Energy:
+    """get_feats.py:167-220 on the device: per frame ``sqrt(clip(sum_bins |STFT|^2, 1e-10))``, reduced in the kernel that
+    reads the frame's spectrum (``pk_mel_run`` what = 3)."""
+
+    def __init__(self, sr=24000, n_fft=2048, hop_length=300, win_length=None, window="hann", center=True,
+                 pad_mode="reflect"):
+        if pad_mode != "reflect":
+            raise NotImplementedError("only pad_mode='reflect' is implemented")
+        self.sr, self.n_fft, self.hop_length, self.win_length = sr, n_fft, hop_length, win_length
+        self.window, self.center, self.pad_mode = window, center, pad_mode
+        self._eng = _Engine(n_fft, hop_length, win_length or n_fft, window, center, False, None, 0)
+
+    def _calculate_energy(self, input):   # noqa: A002  (the reference's argument name)
+        return wrap(self._eng.run([input], 3)[0][:, 0])
+
+    def get_energy_batch(self, wavs):
+        return [wrap(o[:, 0]) for o in self._eng.run(list(wavs), 3)]
+
+    def get_energy(self, wav, use_token_averaged_energy=True, duration=None):
+        """(frames,) energy, or with ``duration`` its token averages (T, 1) like the reference's."""
+        energy = self._calculate_energy(wav)
+        if use_token_averaged_energy and duration is not None:
+            energy = wrap(average_by_duration(energy, duration).reshape(-1, 1))
+        return energy
 
 
 def wav_bytes(wav, samplerate, subtype="PCM_16"):

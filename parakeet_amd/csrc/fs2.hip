@@ -150,6 +150,15 @@ __global__ __launch_bounds__(256) void k_add_tone(float* __restrict__ hs, const 
     for (int c = threadIdx.x; c < A; c += blockDim.x) hs[(long)r * A + c] += src[c];
 }
 
+// dst[rowmap[q]] = src[q] for the timeline rows that belong to an utterance: a timeline tensor, packed by utterance
+__global__ __launch_bounds__(128) void k_fs2_pack_rows(const float* __restrict__ src, int O, const int* __restrict__ rowmap,
+                                                       float* __restrict__ dst) {
+    const long q = blockIdx.x;
+    const long o = rowmap[q];
+    if (o < 0) return;
+    for (int c = threadIdx.x; c < O; c += blockDim.x) dst[o * O + c] = src[q * O + c];
+}
+
 typedef pk_fft_dense Dense;
 typedef pk_fft_layer FftLayer;
 typedef pk_fft_timeline Timeline;
@@ -184,6 +193,15 @@ struct pk_fs2 : pk_fft_core {
     std::vector<float> cond_emb;
     int cond_B = 0;
     pk_dbuf d_spk_id, d_spk_emb, d_spk_vec;
+    // targets of the next encode (pk_fs2_set_targets): given durations / pitch / energy, packed by utterance
+    std::vector<long long> cond_dur;
+    std::vector<float> cond_pitch, cond_energy;
+    long cond_tgt_n = 0;
+    bool cond_has_dur = false, cond_has_pitch = false, cond_has_energy = false;
+    pk_dbuf d_tdur, d_tpitch, d_tenergy;           // ... on the token timeline, what k_cumsum / k_regulate read in their place
+    const float* reg_pitch = nullptr;              // pitch / energy of the last encode that k_regulate embeds
+    const float* reg_energy = nullptr;
+    bool decoded = false;                          // before_outs of the last encode is on the device
     size_t out_scale = 0, out_shift = 0;
     bool has_out_affine = false;
     std::vector<float> h_out_scale, h_out_shift;
@@ -510,6 +528,18 @@ extern "C" int pk_fs2_encode(pk_fs2* h, const int64_t* ids, const int32_t* tok_l
     cond_emb.swap(h->cond_emb);
     cond_tone.swap(h->cond_tone);
     h->cond_B = 0;
+    std::vector<long long> tgt_dur;
+    std::vector<float> tgt_pitch, tgt_energy;
+    tgt_dur.swap(h->cond_dur);
+    tgt_pitch.swap(h->cond_pitch);
+    tgt_energy.swap(h->cond_energy);
+    const bool has_dur = h->cond_has_dur, has_pitch = h->cond_has_pitch, has_energy = h->cond_has_energy;
+    const long tgt_n = h->cond_tgt_n;
+    h->cond_has_dur = h->cond_has_pitch = h->cond_has_energy = false;
+    h->cond_tgt_n = 0;
+    h->decoded = false;
+    if ((has_dur || has_pitch || has_energy) && tgt_n != sumT)
+        PK_FAIL(PK_ESHAPE, "pk_fs2_encode: targets were set for %ld tokens, batch has %ld", tgt_n, sumT);
     if (c.spk_embed_dim > 0 && condB > 0 && condB != B)
         PK_FAIL(PK_ESHAPE, "pk_fs2_encode: speakers were set for %d utterances, batch has %d", condB, B);
     if (c.tone_embed_dim > 0 && !cond_tone.empty() && (long)cond_tone.size() != sumT)
@@ -569,10 +599,38 @@ extern "C" int pk_fs2_encode(pk_fs2* h, const int64_t* ids, const int32_t* tok_l
     PK_TRY(h->d_cum.reserve((size_t)tl.rows_alloc * 4));
     PK_TRY(h->d_frames.reserve((size_t)B * 4));
     h->hs_planes_valid = false;
+    // given durations / pitch / energy (pk_fs2_set_targets; _forward's is_inference=False branch :433-442) go onto the token
+    // timeline and stand in for the predictor's output where it is consumed; the predictors run all the same
+    const float* dur_src = h->d_dout.as<float>();
+    h->reg_pitch = h->d_pout.as<float>();
+    h->reg_energy = h->d_eout.as<float>();
+    if (has_dur || has_pitch || has_energy) {
+        std::vector<float> row(tl.rows_alloc);
+        auto place = [&](pk_dbuf& dst, auto&& value) -> int {
+            std::fill(row.begin(), row.end(), 0.f);
+            long o = 0;
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < tok_lens[b]; ++t, ++o) row[tl.seg_start[b] + t] = value(o);
+            return pk_upload(ctx, dst, row.data(), row.size() * sizeof(float));
+        };
+        if (has_dur) {
+            PK_TRY(place(h->d_tdur, [&](long o) { return (float)tgt_dur[o]; }));
+            dur_src = h->d_tdur.as<float>();
+        }
+        if (has_pitch) {
+            PK_TRY(place(h->d_tpitch, [&](long o) { return tgt_pitch[o]; }));
+            h->reg_pitch = h->d_tpitch.as<float>();
+        }
+        if (has_energy) {
+            PK_TRY(place(h->d_tenergy, [&](long o) { return tgt_energy[o]; }));
+            h->reg_energy = h->d_tenergy.as<float>();
+        }
+    }
     PK_TRY(run_predictor(h, h->pitch, tl, hs, 0, 1.f, h->d_pout.as<float>()));
     PK_TRY(run_predictor(h, h->energy, tl, hs, 0, 1.f, h->d_eout.as<float>()));
-    PK_TRY(run_predictor(h, h->dur, tl, hs, 1, alpha, h->d_dout.as<float>()));
-    PK_LAUNCH(ctx, "fs2_cumsum", k_cumsum, dim3(B), dim3(256), 0, h->d_dout.as<float>(), tl.d_seg_start(),
+    // with given durations the head writes DurationPredictor.forward: log domain, masked, unrounded (duration_predictor.py:85-103)
+    PK_TRY(run_predictor(h, h->dur, tl, hs, has_dur ? 0 : 1, alpha, h->d_dout.as<float>()));
+    PK_LAUNCH(ctx, "fs2_cumsum", k_cumsum, dim3(B), dim3(256), 0, dur_src, tl.d_seg_start(),
               tl.d_seg_len(), h->d_cum.as<int>(), h->d_frames.as<int>());
     h->frames.resize(B);
     PK_HIP(hipMemcpyAsync(h->frames.data(), h->d_frames.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -619,8 +677,8 @@ extern "C" int pk_fs2_decode(pk_fs2* h, float* mel_out, int32_t flags) {
         PK_TRY(pk_fft_act_reserve(h->d_dbg_up, tl.rows, A));
         up_dbg = pk_fft_act_ptr(h->d_dbg_up, A);
     }
-    PK_LAUNCH(ctx, "fs2_regulate", k_regulate, dim3(tl.rows), dim3(128), 0, hs_tok, h->d_pout.as<float>(),
-              h->d_eout.as<float>(), h->W(h->pitch_w), h->W(h->pitch_b), h->W(h->energy_w), h->W(h->energy_b),
+    PK_LAUNCH(ctx, "fs2_regulate", k_regulate, dim3(tl.rows), dim3(128), 0, hs_tok, h->reg_pitch,
+              h->reg_energy, h->W(h->pitch_w), h->W(h->pitch_b), h->W(h->energy_w), h->W(h->energy_b),
               h->d_cum.as<int>(), h->tl_tok.d_seg_start(), h->tl_tok.d_seg_len(), tl.d_row_utt(), tl.d_row_pos(),
               h->d_pe.as<float>(), h->alpha_dec, h->xscale, A, x, up_dbg);
     PK_TRY(pk_fft_act_reserve(h->d_zs, tl.rows, A));
@@ -677,6 +735,7 @@ extern "C" int pk_fs2_decode(pk_fs2* h, float* mel_out, int32_t flags) {
             PK_HIP(hipMemcpyAsync(mel_out, d_out, (size_t)sumF * O * 4, hipMemcpyDeviceToHost, ctx->stream));
             PK_HIP(hipStreamSynchronize(ctx->stream));
         }
+        h->decoded = true;
         return PK_OK;
     }
     if (c.postnet_layers == 0) {
@@ -696,6 +755,83 @@ extern "C" int pk_fs2_decode(pk_fs2* h, float* mel_out, int32_t flags) {
     if (flags & PK_HOST_IO) {
         PK_HIP(hipMemcpyAsync(mel_out, d_out, (size_t)sumL * c.odim * 4, hipMemcpyDeviceToHost, ctx->stream));
         PK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    h->decoded = true;
+    return PK_OK;
+}
+
+extern "C" int pk_fs2_read_before(pk_fs2* h, float* before_out, int32_t flags) {
+    if (!h || !before_out) PK_FAIL(PK_EINVAL, "pk_fs2_read_before: NULL argument");
+    if (!h->encoded) PK_FAIL(PK_ESTATE, "pk_fs2_read_before: call pk_fs2_encode and pk_fs2_decode first");
+    const pk_fs2_cfg& c = h->cfg;
+    if (c.postnet_layers == 0)
+        PK_FAIL(PK_ESTATE, "pk_fs2_read_before: the model has no postnet, before_outs is the mel of pk_fs2_decode (fastspeech2.py:460-461)");
+    long sumF = 0;
+    for (int f : h->frames) sumF += (long)f * c.reduction_factor;
+    if (sumF == 0) return PK_OK;
+    if (!h->decoded) PK_FAIL(PK_ESTATE, "pk_fs2_read_before: call pk_fs2_decode first");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const bool wide = c.reduction_factor > 1;
+    const Timeline& tl = wide ? h->tl_frm2 : h->tl_frm;
+    const int* rowmap = wide ? h->d_rowmap2.as<int>() : h->d_rowmap.as<int>();
+    float* d_out = before_out;
+    if (flags & PK_HOST_IO) {
+        PK_TRY(h->d_mel_stage.reserve((size_t)sumF * c.odim * 4));
+        d_out = h->d_mel_stage.as<float>();
+    }
+    PK_LAUNCH(ctx, "fs2_pack_before", k_fs2_pack_rows, dim3(tl.rows), dim3(128), 0, pk_fft_act_ptr(h->d_before, c.odim), c.odim,
+              rowmap, d_out);
+    if (flags & PK_HOST_IO) {
+        PK_HIP(hipMemcpyAsync(before_out, d_out, (size_t)sumF * c.odim * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PK_OK;
+}
+
+extern "C" int pk_fs2_set_targets(pk_fs2* h, const int64_t* durations, const float* pitch, const float* energy, int64_t n) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_fs2_set_targets: handle is NULL");
+    h->cond_dur.clear();
+    h->cond_pitch.clear();
+    h->cond_energy.clear();
+    h->cond_has_dur = h->cond_has_pitch = h->cond_has_energy = false;
+    h->cond_tgt_n = 0;
+    if (!durations && !pitch && !energy) return PK_OK;
+    if (n <= 0) PK_FAIL(PK_EINVAL, "pk_fs2_set_targets: n must be positive");
+    if (durations)
+        for (int64_t i = 0; i < n; ++i) {
+            if (durations[i] < 0) PK_FAIL(PK_EINVAL, "pk_fs2_set_targets: duration %lld of token %lld is negative", (long long)durations[i], (long long)i);
+            if (durations[i] > (1 << 20)) PK_FAIL(PK_EINVAL, "pk_fs2_set_targets: duration %lld of token %lld exceeds 2^20 frames", (long long)durations[i], (long long)i);
+        }
+    if (durations) h->cond_dur.assign(durations, durations + n);
+    if (pitch) h->cond_pitch.assign(pitch, pitch + n);
+    if (energy) h->cond_energy.assign(energy, energy + n);
+    h->cond_has_dur = durations != nullptr;
+    h->cond_has_pitch = pitch != nullptr;
+    h->cond_has_energy = energy != nullptr;
+    h->cond_tgt_n = (long)n;
+    return PK_OK;
+}
+
+extern "C" int pk_fs2_read_predictions(pk_fs2* h, float* d_outs, float* p_outs, float* e_outs, int64_t n) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_fs2_read_predictions: handle is NULL");
+    if (!h->encoded) PK_FAIL(PK_ESTATE, "pk_fs2_read_predictions: call pk_fs2_encode first");
+    const Timeline& tl = h->tl_tok;
+    long sumT = 0;
+    for (int b = 0; b < tl.B; ++b) sumT += tl.seg_len[b];
+    if (n != sumT) PK_FAIL(PK_ESHAPE, "pk_fs2_read_predictions: expected %ld floats per array, got %lld", sumT, (long long)n);
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    PK_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<float> row(tl.rows);
+    float* const dst[3] = {d_outs, p_outs, e_outs};
+    const float* const src[3] = {h->d_dout.as<float>(), h->d_pout.as<float>(), h->d_eout.as<float>()};
+    for (int k = 0; k < 3; ++k) {
+        if (!dst[k]) continue;
+        PK_HIP(hipMemcpy(row.data(), src[k], (size_t)tl.rows * sizeof(float), hipMemcpyDeviceToHost));
+        long o = 0;
+        for (int b = 0; b < tl.B; ++b)
+            for (int t = 0; t < tl.seg_len[b]; ++t, ++o) dst[k][o] = row[tl.seg_start[b] + t];
     }
     return PK_OK;
 }
@@ -787,7 +923,7 @@ extern "C" void pk_fs2_destroy(pk_fs2* h) {
     h->release_core();
     pk_dbuf* bufs[] = {&h->d_hsp, &h->d_hsam, &h->d_pp, &h->d_ppam, &h->d_pamax, &h->d_tok, &h->d_p1, &h->d_p2, &h->d_hs, &h->d_pout, &h->d_eout, &h->d_dout, &h->d_cum, &h->d_frames,
                        &h->d_tone, &h->d_spk_id, &h->d_spk_emb, &h->d_spk_vec, &h->d_before, &h->d_q1, &h->d_q2, &h->d_rowmap, &h->d_dbg_up, &h->d_zs, &h->d_mel_stage,
-                       &h->d_wide, &h->d_rowmap2};
+                       &h->d_wide, &h->d_rowmap2, &h->d_tdur, &h->d_tpitch, &h->d_tenergy};
     for (auto* b : bufs) b->release();
     h->tl_tok.release();
     h->tl_frm.release();

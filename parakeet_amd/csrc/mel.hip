@@ -9,7 +9,9 @@
 // = hop: row r (frame r) = xpad[r*hop .. r*hop + n_fft).  Utterances sit on one padded-sample axis
 // at hop-aligned offsets, so every frame of every utterance is one row of a single GEMM
 // (frames that straddle two utterances are computed and dropped by the row map).
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "pk_gemm.h"
 
@@ -52,6 +54,44 @@ __global__ void k_clip_log(float* __restrict__ y, long n, float floor_v, int bas
     if (i >= n) return;
     const float v = fmaxf(y[i], floor_v);
     y[i] = base10 ? log10f(v) : logf(v);
+}
+
+// Frame energy (get_feats.py Energy._calculate_energy :196-203): energy[rowmap[r]] = sqrt(max(sum_k re^2 + im^2, floor)).
+// One wave per frame, over the re | im row the STFT GEMM left: the power spectrum lives in registers only, no (frames, n_bin)
+// tensor is written or read back.
+__global__ __launch_bounds__(256) void k_frame_energy(const float* __restrict__ reim, int ld_in, int n_bin, int rows,
+                                                      const int* __restrict__ rowmap, float floor_v,
+                                                      float* __restrict__ out) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int o = rowmap[r];
+    if (o < 0) return;
+    const int lane = threadIdx.x & 63;
+    const float* x = reim + (long)r * ld_in;
+    float s = 0.f;
+    for (int k = lane; k < n_bin; k += 64) {
+        const float re = x[k], im = x[n_bin + k];
+        s += re * re + im * im;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if (lane == 0) out[o] = sqrtf(fmaxf(s, floor_v));
+}
+
+// out[t][c] = mean of x[start[t] .. start[t + 1])[c], 0 for an empty span (get_feats.py _average_by_duration :205-214).
+// One wave per token; start is the prefix sum of the durations, clamped to the number of frames like a numpy slice.
+__global__ __launch_bounds__(64) void k_average_by_duration(const float* __restrict__ x, int C, const int* __restrict__ start,
+                                                            float* __restrict__ out) {
+    const int t = blockIdx.x;
+    const int lo = start[t], n = start[t + 1] - lo;
+    const int lane = threadIdx.x;
+    for (int c = 0; c < C; ++c) {
+        float s = 0.f;
+        for (int f = lane; f < n; f += 64) s += x[(long)(lo + f) * C + c];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) out[(long)t * C + c] = n > 0 ? s / (float)n : 0.f;
+    }
 }
 
 }  // namespace
@@ -116,7 +156,7 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
                           int32_t what, int32_t flags) {
     if (!h || !wav || !lens || !out) PK_FAIL(PK_EINVAL, "pk_mel_run: NULL argument");
     if (B <= 0) PK_FAIL(PK_EINVAL, "pk_mel_run: batch size must be positive");
-    if (what < 0 || what > 2) PK_FAIL(PK_EINVAL, "pk_mel_run: what must be 0 (re|im), 1 (spectrum) or 2 (mel)");
+    if (what < 0 || what > 3) PK_FAIL(PK_EINVAL, "pk_mel_run: what must be 0 (re|im), 1 (spectrum), 2 (mel) or 3 (energy)");
     if (what == 2 && h->cfg.n_mels <= 0) PK_FAIL(PK_ESTATE, "pk_mel_run: no mel basis was given");
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
@@ -157,7 +197,7 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
     PK_HIP(hipStreamSynchronize(ctx->stream));
     const int* d_tab = h->ws_tab.as<int>();
     const float* d_wav = wav;
-    const int out_cols = what == 0 ? 2 * nb : (what == 1 ? nb : c.n_mels);
+    const int out_cols = what == 0 ? 2 * nb : (what == 1 ? nb : (what == 2 ? c.n_mels : 1));
     float* d_out = out;
     if (flags & PK_HOST_IO) {
         PK_TRY(h->ws_wav.reserve((size_t)sumS * 4));
@@ -192,7 +232,10 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
         g.C = h->ws_reim.as<float>();
         g.ldc = 2 * nb;
         PK_TRY(pk_gemm_launch(ctx, "mel_stft_gemm", g));
-        if (what == 1) {
+        if (what == 3) {
+            PK_LAUNCH(ctx, "mel_frame_energy", k_frame_energy, dim3(pk_div_up(rows, 4)), dim3(256), 0, h->ws_reim.as<float>(),
+                      2 * nb, nb, rows, d_tab + 2 * B, c.log_floor, d_out);
+        } else if (what == 1) {
             // spectrum straight into the packed output (row map applied by a tiny second pass: reuse k_magnitude
             // on timeline rows, then gather) -- keep it simple: compute on the timeline, gather rows with a GEMM-free copy
             PK_TRY(h->ws_spec.reserve((size_t)rows_alloc * h->ldspec * 4));
@@ -234,6 +277,30 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
         PK_HIP(hipStreamSynchronize(ctx->stream));
     }
     return PK_OK;
+}
+
+extern "C" int pk_op_average_by_duration(pk_ctx* ctx, const float* x, int64_t frames, int32_t C, const int64_t* durations,
+                                         int32_t T, float* out) {
+    if (!ctx || !durations || !out || (!x && frames > 0)) PK_FAIL(PK_EINVAL, "pk_op_average_by_duration: NULL argument");
+    if (frames < 0 || frames > 0x7fffffff || C <= 0 || T <= 0) PK_FAIL(PK_EINVAL, "average_by_duration: bad shape");
+    PK_DEVICE(ctx->device);
+    std::vector<int> start(T + 1, 0);
+    int64_t k = 0;
+    for (int t = 0; t < T; ++t) {
+        if (durations[t] < 0) PK_FAIL(PK_EINVAL, "average_by_duration: negative duration at token %d", t);
+        k = std::min<int64_t>(k + durations[t], frames);   // x[start:end] past the last frame is an empty slice
+        start[t + 1] = (int)k;
+    }
+    pk_dbuf d_start;
+    int rc = pk_upload(ctx, d_start, start.data(), start.size() * sizeof(int));
+    if (rc == PK_OK) {
+        hipLaunchKernelGGL(k_average_by_duration, dim3(T), dim3(64), 0, ctx->stream, x, C, d_start.as<int>(), out);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // d_start is released below
+        if (e != hipSuccess) { d_start.release(); PK_FAIL(PK_EHIP, "pk_op_average_by_duration: %s", hipGetErrorString(e)); }
+    }
+    d_start.release();
+    return rc;
 }
 
 extern "C" void pk_mel_destroy(pk_mel* h) {

@@ -4,10 +4,13 @@ Mirrors parakeet/models/fastspeech2/fastspeech2.py: ``FastSpeech2`` (constructor
 kwargs :52-118, ``set_state_dict``, ``eval``, ``inference`` :468-558) and
 ``FastSpeech2Inference`` (:662-671).  All arithmetic runs in libpk_synth.so
 (csrc/fs2.hip on the transformer machinery of csrc/fft.hip, csrc/gemm.hip).
-Training (``forward`` / loss) is out of scope.
+``forward`` (:286-375) and ``inference(use_teacher_forcing=True)`` run ``_forward(..., ds, ps, es,
+is_inference=False)`` (:433-442) with given durations, pitch and energy; the losses are out of scope.
 
-Extension over the reference: ``inference_batch`` runs a ragged batch in one
-engine call (the reference's ``inference`` is one utterance per call).
+Extensions over the reference: ``inference_batch`` runs a ragged batch in one engine call (the
+reference's ``inference`` is one utterance per call), ``teacher_forced_batch`` does the same with given
+targets, ``predict_batch`` returns the predicted durations / pitch / energy without decoding, and
+``inference_batch(durations=, pitch=, energy=)`` synthesises with edited ones (prosody control).
 """
 import ctypes as C
 
@@ -16,6 +19,10 @@ import torch
 
 from . import _capi
 from .runtime import Context, dptr, set_params, to_numpy_f32, wrap
+
+
+def _host(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
 
 
 class FastSpeech2:
@@ -88,6 +95,7 @@ class FastSpeech2:
         cfg.tone_embed_integration_type = 0
         self.tone_embed_dim = tone_embed_dim
         self.spk_embed_dim = spk_embed_dim
+        self._postnet_layers = postnet_layers
         h = C.c_void_p()
         _capi.check(self._ctx.lib.pk_fs2_create(self._ctx.handle, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -140,13 +148,30 @@ class FastSpeech2:
         _capi.check(self._ctx.lib.pk_fs2_set_debug(self._h, 1 if on else 0))
 
     # -- synthesis -----------------------------------------------------------
-    def encode_batch(self, texts, alpha=1.0, spk_ids=None, spembs=None, tone_ids=None):
+    def encode_batch(self, texts, alpha=1.0, spk_ids=None, spembs=None, tone_ids=None, durations=None, pitch=None,
+                     energy=None):
         """Phase 1: returns the per-utterance frame counts (host ints).  ``spk_ids`` (B,) ints or
-        ``spembs`` (B, spk_embed_dim): speaker conditioning of a multi-speaker model (:396-402)."""
+        ``spembs`` (B, spk_embed_dim): speaker conditioning of a multi-speaker model (:396-402).
+        ``durations`` / ``pitch`` / ``energy``: lists of per-utterance (T,) or (T, 1) arrays that stand in for the
+        predictor's values (``pk_fs2_set_targets``); given durations are used as they are, ``alpha`` does not scale them."""
         ctx = Context.get(self._ctx.device)
         self._finalize()
         ids = [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t).astype(np.int64).reshape(-1)
                for t in texts]
+        if durations is not None or pitch is not None or energy is not None:
+            def pack(name, vals, dtype):
+                if vals is None:
+                    return None
+                vals = [_host(v).reshape(-1) for v in vals]
+                if [len(v) for v in vals] != [len(i) for i in ids]:
+                    raise ValueError(f"{name}: one value per token of every utterance is needed, got lengths "
+                                     f"{[len(v) for v in vals]} for {[len(i) for i in ids]} tokens")
+                return np.ascontiguousarray(np.concatenate(vals).astype(dtype))
+            d, p, e = pack("durations", durations, np.int64), pack("pitch", pitch, np.float32), pack(
+                "energy", energy, np.float32)
+            targets = (d, p, e)
+        else:
+            targets = None
         if self.tone_embed_dim is not None and tone_ids is not None:
             tn = [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t).astype(np.int64).reshape(-1)
                   for t in tone_ids]
@@ -166,6 +191,11 @@ class FastSpeech2:
         lens = np.array([len(i) for i in ids], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate(ids))
         frames = np.zeros(len(ids), dtype=np.int32)
+        if targets is not None:      # last, so that nothing can fail between this and the encode that consumes it
+            d, p, e = targets
+            _capi.check(ctx.lib.pk_fs2_set_targets(
+                self._h, None if d is None else d.ctypes.data_as(C.POINTER(C.c_int64)),
+                None if p is None else _capi.fptr(p), None if e is None else _capi.fptr(e), flat.size))
         _capi.check(ctx.lib.pk_fs2_encode(self._h, flat.ctypes.data_as(C.POINTER(C.c_int64)),
                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
                                           C.c_float(alpha), frames.ctypes.data_as(C.POINTER(C.c_int32))))
@@ -182,28 +212,136 @@ class FastSpeech2:
             _capi.check(ctx.lib.pk_fs2_decode(self._h, dptr(mel), _capi.PK_APPLY_NORMALIZER if denormalize else 0))
         return mel
 
-    def inference_batch(self, texts, alpha=1.0, spk_ids=None, spembs=None, tone_ids=None, denormalize=False):
-        frames = self.encode_batch(texts, alpha, spk_ids, spembs, tone_ids)
-        mel = self.decode_packed(denormalize)
+    def before_packed(self):
+        """Packed (sum(frames), odim) ``before_outs`` (:457) of the last decode, never de-normalised."""
+        ctx = Context.get(self._ctx.device)
+        total = int(sum(self._last_frames))
+        if self._postnet_layers == 0:        # after_outs IS before_outs (:460-461)
+            return self.decode_packed(False)
+        out = ctx.empty((total, self.odim))
+        if total:
+            _capi.check(ctx.lib.pk_fs2_read_before(self._h, dptr(out), 0))
+        return out
+
+    def read_predictions(self):
+        """``(d_outs, p_outs, e_outs)`` of the last encode, one float32 (T,) host array per utterance each.  ``d_outs``: the
+        integer durations of the inference branch (``alpha`` applied), or, when durations were given, the duration
+        predictor's log-domain output (``DurationPredictor.forward``)."""
+        n = int(sum(self._last_tok))
+        d, p, e = (np.empty(n, dtype=np.float32) for _ in range(3))
+        _capi.check(self._ctx.lib.pk_fs2_read_predictions(self._h, _capi.fptr(d), _capi.fptr(p), _capi.fptr(e), n))
+        cuts = np.cumsum(self._last_tok)[:-1]
+        return np.split(d, cuts), np.split(p, cuts), np.split(e, cuts)
+
+    def _split(self, packed, frames):
         outs, o = [], 0
         for f in frames:
-            outs.append(wrap(mel[o:o + int(f)]))
+            outs.append(wrap(packed[o:o + int(f)]))
             o += int(f)
         return outs
 
+    def inference_batch(self, texts, alpha=1.0, spk_ids=None, spembs=None, tone_ids=None, denormalize=False, *,
+                        durations=None, pitch=None, energy=None):
+        """One encode and one decode for a ragged batch; every utterance is evaluated as if it were alone.
+        ``durations`` / ``pitch`` / ``energy`` (keyword only; each a list of per-utterance arrays or None) override the
+        predicted values: read them with ``predict_batch``, edit, and synthesise with the edited ones."""
+        frames = self.encode_batch(texts, alpha, spk_ids, spembs, tone_ids, durations, pitch, energy)
+        return self._split(self.decode_packed(denormalize), frames)
+
+    def predict_batch(self, texts, alpha=1.0, spk_ids=None, spembs=None, tone_ids=None):
+        """Per utterance ``(durations int64 (T,), pitch (T,), energy (T,))`` of the inference branch (:423-425; the durations
+        carry ``alpha``).  One encode, no decode."""
+        self.encode_batch(texts, alpha, spk_ids, spembs, tone_ids)
+        d, p, e = self.read_predictions()
+        return [(db.astype(np.int64), pb, eb) for db, pb, eb in zip(d, p, e)]
+
+    def teacher_forced_batch(self, texts, durations, pitch, energy, spk_ids=None, spembs=None, tone_ids=None,
+                             denormalize=False, return_before=False):
+        """``_forward(xs, ilens, olens, ds, ps, es, is_inference=False)`` (:433-442) for a ragged batch in one encode and one
+        decode: the ground-truth-aligned mel of every utterance, (r * sum(d), odim) each (``(before_outs, after_outs)`` pairs
+        with ``return_before``).  Every utterance is evaluated as if it were alone, like ``inference_batch``.  Tone ids are the
+        per-token ids ``inference`` forwards."""
+        if durations is None or pitch is None or energy is None:
+            raise ValueError("teacher forcing needs durations, pitch and energy")
+        frames = self.encode_batch(texts, 1.0, spk_ids, spembs, tone_ids, durations, pitch, energy)
+        after = self._split(self.decode_packed(denormalize), frames)
+        if not return_before:
+            return after
+        return list(zip(self._split(self.before_packed(), frames), after))
+
+    def forward(self, text, text_lengths, speech, speech_lengths, durations, pitch, energy, tone_id=None, spembs=None,
+                spk_id=None):
+        """fastspeech2.py:286-375: padded batch in, ``(before_outs, after_outs, d_outs, p_outs, e_outs, ys, olens)`` out
+        (padded, zeros in padded rows; ``ys`` / ``olens`` trimmed to a multiple of ``reduction_factor`` as at :369-373).
+
+        The engine evaluates every utterance as if it were alone; the reference's batched ``forward`` lets padded rows
+        reach the last valid rows of a shorter utterance through the k = 3 convolutions.  The result therefore equals the
+        reference's for each utterance taken alone, and for a batch of equal lengths -- the contract ``inference_batch``
+        has.  ``d_outs`` is the duration predictor's log-domain output (``DurationPredictor.forward``)."""
+        if tone_id is not None:
+            raise NotImplementedError(
+                "tone_id in forward(): the reference's batched branch normalises the (B, T, D) tone embeddings over the "
+                "TIME axis (F.normalize's default axis 1, fastspeech2.py:596), not over the features as inference()'s 1-D "
+                "ids do; use teacher_forced_batch(tone_ids=...) for the per-token reading")
+        r = self.reduction_factor
+        xs = _host(text).astype(np.int64)
+        ilens = [int(v) for v in _host(text_lengths).reshape(-1)]
+        olens = np.array([int(v) for v in _host(speech_lengths).reshape(-1)], dtype=np.int64)
+        ds = _host(durations).astype(np.int64)
+        ps = _host(pitch).astype(np.float32).reshape(ds.shape)
+        es = _host(energy).astype(np.float32).reshape(ds.shape)
+        B = len(ilens)
+        for b in range(B):
+            if int(olens[b]) // r != int(ds[b, :ilens[b]].sum()):
+                raise ValueError(f"utterance {b}: speech_lengths // reduction_factor = {int(olens[b]) // r} frames, the "
+                                 f"durations sum to {int(ds[b, :ilens[b]].sum())}")
+        sel = [slice(0, n) for n in ilens]
+        frames = self.encode_batch(
+            [xs[b, sel[b]] for b in range(B)], 1.0,
+            None if spk_id is None or spembs is not None else _host(spk_id).reshape(-1),
+            None if spembs is None else to_numpy_f32(spembs).reshape(B, -1), None,
+            [ds[b, sel[b]] for b in range(B)], [ps[b, sel[b]] for b in range(B)], [es[b, sel[b]] for b in range(B)])
+        after = self._split(self.decode_packed(False), frames)
+        before = self._split(self.before_packed(), frames)
+        d, p, e = self.read_predictions()
+        ctx = Context.get(self._ctx.device)
+        Lmax, Tmax = int(max(frames)), xs.shape[1]
+        before_outs = torch.zeros((B, Lmax, self.odim), dtype=torch.float32, device=ctx.device)
+        after_outs = torch.zeros_like(before_outs)
+        d_outs = torch.zeros((B, Tmax), dtype=torch.float32)
+        p_outs, e_outs = torch.zeros((B, Tmax, 1), dtype=torch.float32), torch.zeros((B, Tmax, 1), dtype=torch.float32)
+        for b in range(B):
+            before_outs[b, :int(frames[b])] = before[b]
+            after_outs[b, :int(frames[b])] = after[b]
+            d_outs[b, :ilens[b]] = torch.from_numpy(d[b])
+            p_outs[b, :ilens[b], 0] = torch.from_numpy(p[b])
+            e_outs[b, :ilens[b], 0] = torch.from_numpy(e[b])
+        ys = speech
+        olens_out = torch.from_numpy(olens)
+        if r > 1:                                     # :369-373
+            olens_out = torch.from_numpy(olens - olens % r)
+            ys = ys[:, :int(olens_out.max())]
+        return wrap(before_outs), wrap(after_outs), wrap(d_outs), wrap(p_outs), wrap(e_outs), ys, olens_out
+
     def inference(self, text, speech=None, durations=None, pitch=None, energy=None, alpha=1.0,
                   use_teacher_forcing=False, spembs=None, spk_id=None, tone_id=None, denormalize=False):
-        """(T,) int64 -> (L, odim); fastspeech2.py:468-558 (is_inference=True branch)."""
+        """(T,) int64 -> (L, odim); fastspeech2.py:468-558.  ``use_teacher_forcing=True`` needs ``durations`` (T,), ``pitch``
+        and ``energy`` ((T,) or (T, 1)) and computes ``_forward(ds, ps, es, is_inference=False)`` with them for any T
+        (``alpha`` is not applied, as in the reference; its ``if durations:`` at :516 is what stops the reference's own
+        wrapper for T > 1).  Without the switch the three are ignored, as in the reference."""
+        kw = {}
         if use_teacher_forcing:
-            raise NotImplementedError("teacher forcing is a training-time path")
+            if durations is None or pitch is None or energy is None:
+                raise ValueError("use_teacher_forcing=True needs durations, pitch and energy")
+            kw = dict(durations=[durations], pitch=[pitch], energy=[energy])
         tones = None if tone_id is None else [tone_id]   # (T,) ids, forwarded un-batched by the reference (:546,556)
         if spembs is not None:      # (spk_embed_dim,), unsqueezed by the reference (:541-542)
             return self.inference_batch([text], alpha, spembs=to_numpy_f32(spembs).reshape(1, -1), tone_ids=tones,
-                                        denormalize=denormalize)[0]
+                                        denormalize=denormalize, **kw)[0]
         if spk_id is not None:
             sid = np.asarray(spk_id.cpu() if isinstance(spk_id, torch.Tensor) else spk_id).reshape(-1)[:1]
-            return self.inference_batch([text], alpha, spk_ids=sid, tone_ids=tones, denormalize=denormalize)[0]
-        return self.inference_batch([text], alpha, tone_ids=tones, denormalize=denormalize)[0]
+            return self.inference_batch([text], alpha, spk_ids=sid, tone_ids=tones, denormalize=denormalize, **kw)[0]
+        return self.inference_batch([text], alpha, tone_ids=tones, denormalize=denormalize, **kw)[0]
 
     def debug_tap(self, what, b):
         n_rows = self._last_tok[b] if what <= 3 else self._last_frames[b]
