@@ -17,7 +17,8 @@
  *   pk_wf_*     parakeet/models/waveflow.py ConditionalWaveFlow.infer :785-805
  *   pk_tts_*    parakeet/models/transformer_tts/transformer_tts.py TransformerTTS.inference :511-647,
  *               TransformerTTSInference.forward :757-767
- *   pk_taco_*   parakeet/models/tacotron2.py Tacotron2.infer :781-840 (Tacotron2Decoder.infer :474-541)
+ *   pk_taco_*   parakeet/models/tacotron2.py Tacotron2.infer :781-840 (Tacotron2Decoder.infer :474-541),
+ *               Tacotron2.forward :691-778 (Tacotron2Decoder.forward :419-472)
  *   pk_spk_*    parakeet/models/lstm_speaker_encoder.py LSTMSpeakerEncoder.embed_sequences / embed_utterance :40-53
  *   pk_stft_mel parakeet/modules/audio.py STFT.magnitude :202-215 + MelScale :226-229,
  *               parakeet/data/get_feats.py LogMelFBank.get_log_mel_fbank :80-88
@@ -548,7 +549,7 @@ int pk_taco_set_math(pk_taco* h, int32_t mode);
  * (step * 2 + layer) * d_prenet + unit for decoding step 0, 1, ...; 0 = no dropout (not what the reference computes). */
 int pk_taco_set_dropout(pk_taco* h, int32_t on);
 int pk_taco_finalize(pk_taco* h);
-/* Global condition of the NEXT pk_taco_infer call (:816-821): g HOST float32 (B, d_global_condition), one row per
+/* Global condition of the NEXT pk_taco_infer / pk_taco_teacher call (:816-821): g HOST float32 (B, d_global_condition), one row per
  * utterance, concatenated to every encoder output row of that utterance.  Consumed by that call; NULL clears it.
  * A model with d_global_condition > 0 refuses to infer without it (the reference fails on the shapes). */
 int pk_taco_set_global_condition(pk_taco* h, const float* g, int32_t B);
@@ -561,7 +562,20 @@ int pk_taco_set_global_condition(pk_taco* h, const float* g, int32_t B);
  *   out_frames   (B) host: decoder steps L_b */
 int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
                   int32_t max_decoder_steps, const uint64_t* seeds, int32_t flags, int32_t* out_frames);
-/* Outputs of the last pk_taco_infer (:825-838), each packed by utterance, any of them may be NULL:
+/* Tacotron2.forward (:691-778) with eval semantics for a packed batch, up to the postnet: the decoder is teacher-forced
+ * (Tacotron2Decoder.forward :419-472), the query of step s is [0, mels[0], ..., mels[L_b - 2]][s] and not the decoder's
+ * own previous output; exactly L_b steps, no stop rule (with a stop token the logit of every step is recorded).  The
+ * prenet of all sum(L_b) query rows runs in one launch before the loop, every row bit-identical to what pk_taco_infer's
+ * per-step prenet gives for the same query, step and seed; the loop of max(L_b) steps is enqueued without a host poll.
+ *   ids / tones / tok_lens / seeds  as pk_taco_infer
+ *   mels         packed (sum(L_b), d_mels) float32 in the model's mel domain; device, or host under PK_HOST_IO
+ *   frame_lens   HOST (B) teacher frames L_b >= 1
+ *   out_frames   (B) host: L_b
+ * Consumes the pending pk_taco_set_global_condition rows like pk_taco_infer.  pk_taco_read and pk_taco_debug_read then
+ * serve its result. */
+int pk_taco_teacher(pk_taco* h, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
+                    const float* mels, const int32_t* frame_lens, const uint64_t* seeds, int32_t flags, int32_t* out_frames);
+/* Outputs of the last pk_taco_infer or pk_taco_teacher (:825-838), each packed by utterance, any of them may be NULL:
  *   mel_output (sum(L_b), d_mels); mel_outputs_postnet = mel_output + postnet(mel_output), same shape;
  *   alignments: per utterance (L_b, T_b); stop_logits (sum(L_b)), only with a stop token.
  * flags: PK_HOST_IO if they are host pointers. */

@@ -72,6 +72,8 @@ struct pk_rowgemm_args {
     // stop_kind 1 = Tacotron2's rule (models/tacotron2.py:515-528 with use_stop_token): the raw logit s is stored at
     // stop_probs[stop_step * M + m] (stop_step counted from 0), the utterance ends when sigmoid(s) > 0.5 or
     // stop_step + 1 >= stop_max_steps: stop_len[m] = stop_step + 1.  No LayerNorm, any K.
+    // stop_kind 2 = the logit of kind 1 alone (Tacotron2 with teacher forcing: recorded for every step, ends nothing;
+    // stop_len / stop_ndone are not touched and may be NULL).
     const float* stop_w = nullptr;
     float stop_bias = 0.f, stop_thr = 0.5f;
     int stop_kind = 0, stop_max_steps = 0;

@@ -20,6 +20,11 @@
 // PK_AR_ROWGEMM=0 selects the tile GEMM.  LocationSensitiveAttention is three launches (see LsaArgs).
 // Stop rules run on the device (k_taco_stop); a finished utterance keeps being stepped and is ignored.
 //
+// Teacher forcing (pk_taco_teacher; Tacotron2.forward :691-778, Tacotron2Decoder.forward :419-472): the queries are
+// [0, mel[0], ..., mel[L - 2]], known before the first step, so the prenet leaves the loop (k_taco_teacher_prenet: every
+// row of the ragged batch in one launch, each row in the accumulation order of the per-step kernel) and the loop of
+// max L_b steps is enqueued in one go: no stop rule, no host poll.
+//
 // LSTM semantics [paddle-semantics, from Paddle's API documentation]: gate order i, f, g, o along the 4H axis.
 // Dropout: include/pk_synth.h "dropout stream"; only the decoder prenet's stays on at inference (:76-79).
 #include <algorithm>
@@ -284,6 +289,7 @@ __global__ __launch_bounds__(256) void k_taco_lsa_ctx(LsaArgs a) {
 //   without: the argmax of this step's alignment sits on the last memory position for the first time -> remember the
 //   step; again at a step more than 20 later -> end;
 //   always: step + 1 == max_steps.
+// len == NULL (teacher forcing, with a stop token only): the logit is recorded and nothing ends.
 __global__ __launch_bounds__(256) void k_taco_stop(const float* __restrict__ hc, int ld, int n, const float* __restrict__ w,
                                                    float bias, int use_stop, int B, int step, int max_steps,
                                                    const float* __restrict__ attw, const int* __restrict__ seg_start,
@@ -327,10 +333,128 @@ __global__ __launch_bounds__(256) void k_taco_stop(const float* __restrict__ hc,
         }
     }
     if (step + 1 >= max_steps) end = true;
-    if (lane == 0 && end && len[b] == 0) {
+    if (lane == 0 && len && end && len[b] == 0) {
         len[b] = step + 1;
         atomicAdd(ndone, 1);
     }
+}
+
+// Teacher forcing: the decoder prenet of EVERY frame of the ragged batch in one launch (DecoderPreNet.forward :61-79 on
+// the shifted queries of Tacotron2Decoder.forward :444-451).  Packed frame g of utterance b at step s = g - frm_off[b]:
+//   query = s == 0 ? 0 : teacher[g - 1];   out[(s * B + b)] = dropout(relu(dropout(relu(query W1)) W2))
+// with the dropout stream's element index ((s * 2 + layer) * U + unit) and the utterance's seed -- what k_ar_prenet_embed
+// (pk_ar.h) computes for the same query at decoding step s, BIT FOR BIT: a thread owns the same 4 outputs and the same
+// slice of K as there (pk_ar_dense_phase), walks it in the same order with one fmaf chain per row, and the parts are summed
+// through LDS in the same order.  What changes is that a workgroup holds TP_R rows, so a weight float4 that is loaded once
+// feeds TP_R chains (a workgroup per row read the 344 KB of the two LJSpeech matrices from L2 for every frame).
+// w1 == NULL: the query rows themselves are the result (U = M; for the per-step prenet paths that are not this kernel's twin).
+constexpr int TP_R = 4;
+struct TeacherPrenetArgs {
+    const float* teacher;             // packed [total][M]
+    const int* frm_off;               // [B + 1]
+    int B, M, U, total;
+    const float *w1, *w2;             // [M][U], [U][U] row-major
+    float* out; int ldo;              // position-major rows s * B + b
+    int dropout; const unsigned long long* seeds; unsigned thr; float scale;
+};
+__device__ __forceinline__ void tp_dense_phase(const float* in, int K, const float* __restrict__ W, int N, float* red, int tid) {
+    const int ng = N >> 2, n4 = tid % ng, part = tid / ng, nparts = 512 / ng;
+    const int kper = (K + nparts - 1) / nparts, kbeg = part * kper, kend = min(K, kbeg + kper);
+    const float4* W4 = reinterpret_cast<const float4*>(W);
+    float4 acc[TP_R];
+#pragma unroll
+    for (int r = 0; r < TP_R; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // (batches of 16 weight loads, not 32 as there: TP_R accumulators share the registers; a padded step adds 0 * w, so the
+    // chain of every row is the same whatever the batch)
+    for (int k0 = kbeg; k0 < kend; k0 += 16) {
+        float4 w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = W4[(long)min(k0 + i, kend - 1) * ng + n4];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+#pragma unroll
+            for (int r = 0; r < TP_R; ++r) {
+                const float x = k0 + i < kend ? in[r * 512 + k0 + i] : 0.f;
+                acc[r].x = fmaf(x, w[i].x, acc[r].x);
+                acc[r].y = fmaf(x, w[i].y, acc[r].y);
+                acc[r].z = fmaf(x, w[i].z, acc[r].z);
+                acc[r].w = fmaf(x, w[i].w, acc[r].w);
+            }
+        }
+    }
+    if (part < nparts) {
+#pragma unroll
+        for (int r = 0; r < TP_R; ++r) *reinterpret_cast<float4*>(red + r * 2048 + part * N + 4 * n4) = acc[r];
+    }
+}
+__global__ __launch_bounds__(512) void k_taco_teacher_prenet(TeacherPrenetArgs a) {
+    __shared__ __attribute__((aligned(16))) float hin[TP_R * 512];
+    __shared__ __attribute__((aligned(16))) float red[TP_R * 2048];
+    __shared__ int rb[TP_R], rs[TP_R];
+    const int tid = threadIdx.x;
+    const long g0 = (long)blockIdx.x * TP_R;
+    if (tid < TP_R) {
+        const long g = g0 + tid;
+        int b = -1, s = 0;
+        if (g < a.total) {
+            b = 0;
+            while (b + 1 < a.B && a.frm_off[b + 1] <= g) ++b;
+            s = (int)(g - a.frm_off[b]);
+        }
+        rb[tid] = b;
+        rs[tid] = s;
+    }
+    __syncthreads();
+    for (int q = tid; q < TP_R * a.M; q += 512) {
+        const int r = q / a.M, c = q - r * a.M;
+        const bool teacher_row = rb[r] >= 0 && rs[r] > 0;   // step 0 reads the zero frame (:447-449)
+        hin[r * 512 + c] = teacher_row ? a.teacher[(g0 + r - 1) * a.M + c] : 0.f;
+    }
+    __syncthreads();
+    if (!a.w1) {   // (uniform)
+        for (int q = tid; q < TP_R * a.M; q += 512) {
+            const int r = q / a.M, c = q - r * a.M;
+            if (rb[r] >= 0) a.out[((long)rs[r] * a.B + rb[r]) * a.ldo + c] = hin[r * 512 + c];
+        }
+        return;
+    }
+    const int N = a.U, ng = N >> 2, nparts = 512 / ng;
+    for (int j = 0; j < 2; ++j) {
+        tp_dense_phase(hin, j == 0 ? a.M : a.U, j == 0 ? a.w1 : a.w2, N, red, tid);
+        __syncthreads();
+        for (int q = tid; q < TP_R * ng; q += 512) {
+            const int r = q / ng, c = q - r * ng;
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int p = 0; p < nparts; ++p) {
+                const float4 v = *reinterpret_cast<const float4*>(red + r * 2048 + p * N + 4 * c);
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+            s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f);
+            if (a.dropout && rb[r] >= 0) {
+                const unsigned long long e = ((unsigned long long)rs[r] * 2ull + (unsigned long long)j) * (unsigned long long)N + 4ull * c;
+                unsigned w4[4];
+                pk_dropout_words(e, a.seeds ? a.seeds[rb[r]] : 0ull, w4);
+                s.x = w4[0] >= a.thr ? s.x * a.scale : 0.f;
+                s.y = w4[1] >= a.thr ? s.y * a.scale : 0.f;
+                s.z = w4[2] >= a.thr ? s.z * a.scale : 0.f;
+                s.w = w4[3] >= a.thr ? s.w * a.scale : 0.f;
+            }
+            *reinterpret_cast<float4*>(hin + r * 512 + 4 * c) = s;
+        }
+        __syncthreads();
+    }
+    for (int q = tid; q < TP_R * ng; q += 512) {
+        const int r = q / ng, c = q - r * ng;
+        if (rb[r] >= 0)
+            *reinterpret_cast<float4*>(a.out + ((long)rs[r] * a.B + rb[r]) * a.ldo + 4 * c) = *reinterpret_cast<const float4*>(hin + r * 512 + 4 * c);
+    }
+}
+
+// This step's precomputed prenet rows -> the first slice of the attention LSTM's operand rows: grid B, U / 4 threads
+__global__ __launch_bounds__(128) void k_taco_prenet_rows(const float* __restrict__ src, int U, float* __restrict__ dst, int ld) {
+    const int b = blockIdx.x;
+    for (int c = threadIdx.x; c < (U >> 2); c += blockDim.x)
+        *reinterpret_cast<float4*>(dst + (long)b * ld + 4 * c) = *reinterpret_cast<const float4*>(src + (long)b * U + 4 * c);
 }
 }  // namespace
 
@@ -360,7 +484,7 @@ struct pk_taco : pk_fft_core {
     pk_dbuf d_gc, d_enc;
     pk_dbuf d_tok, d_tone, d_e1, d_e2, d_xg, d_mem, d_pkey, d_attw, d_cum, d_in1, d_in1b, d_in2, d_in2b, d_in3, d_p1, d_gates, d_catt,
         d_cdec, d_zero, d_y, d_pq, d_energy, d_logits, d_state, d_seeds, d_align, d_alignoff, d_before, d_q1, d_q2, d_rowmap, d_stage,
-        d_stage2;
+        d_stage2, d_teacher, d_frmoff, d_pre;
 };
 
 namespace {
@@ -596,42 +720,54 @@ extern "C" int pk_taco_finalize(pk_taco* h) {
 namespace {
 constexpr int SLACK = 2 * PK_GEMM_BM;   // rows a GEMM tile may read beyond the rows it was asked for
 int rows_reserve(pk_dbuf& buf, long rows, int C) { return pk_fft_act_reserve(buf, (int)(rows + SLACK), C); }
-}  // namespace
 
-extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
-                             int32_t max_decoder_steps, const uint64_t* seeds, int32_t flags, int32_t* out_frames) {
-    (void)flags;
-    if (!h) PK_FAIL(PK_EINVAL, "pk_taco_infer: NULL argument");
+// pk_taco_infer (teacher == NULL: the decoder feeds itself and the stop rules end it within max_decoder_steps) and
+// pk_taco_teacher (the queries are the teacher's frames, frame_lens[b] steps, max_decoder_steps = max frame_lens)
+int taco_run(pk_taco* h, const char* fn, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
+             int32_t max_decoder_steps, const uint64_t* seeds, const float* teacher, const int32_t* frame_lens, int32_t flags,
+             int32_t* out_frames) {
     // the per-call conditioning is consumed by this call, whatever happens next
     std::vector<float> cond_g;
     cond_g.swap(h->cond_g);
     const int condB = h->cond_B;
     h->cond_B = 0;
-    if (!ids || !tok_lens || !out_frames) PK_FAIL(PK_EINVAL, "pk_taco_infer: NULL argument");
-    if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_taco_infer: call pk_taco_finalize first");
-    if (B <= 0) PK_FAIL(PK_EINVAL, "pk_taco_infer: batch size must be positive");
-    if (max_decoder_steps <= 0) PK_FAIL(PK_EINVAL, "pk_taco_infer: max_decoder_steps must be positive");
+    if (!ids || !tok_lens || !out_frames) PK_FAIL(PK_EINVAL, "%s: NULL argument", fn);
+    if (!h->finalized) PK_FAIL(PK_ESTATE, "%s: call pk_taco_finalize first", fn);
+    if (B <= 0) PK_FAIL(PK_EINVAL, "%s: batch size must be positive", fn);
+    if (max_decoder_steps <= 0) PK_FAIL(PK_EINVAL, "%s: max_decoder_steps must be positive", fn);
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     const pk_taco_cfg& c = h->cfg;
-    if (c.n_tones > 0 && !tones) PK_FAIL(PK_EINVAL, "pk_taco_infer: the model has a tone embedding, tones are required (:809-810)");
-    if (c.n_tones <= 0 && tones) PK_FAIL(PK_ESTATE, "pk_taco_infer: the model has no tone embedding");
+    if (c.n_tones > 0 && !tones) PK_FAIL(PK_EINVAL, "%s: the model has a tone embedding, tones are required (:809-810)", fn);
+    if (c.n_tones <= 0 && tones) PK_FAIL(PK_ESTATE, "%s: the model has no tone embedding", fn);
     const int E = c.d_encoder, Hh = E / 2, M = c.d_mels, Pn = c.d_prenet, Ha = c.d_attention_rnn, Hd = c.d_decoder_rnn,
               Da = c.d_attention, G = c.d_global_condition, Eg = E + G;
     if (G > 0 && condB != B)
-        PK_FAIL(PK_EINVAL, "pk_taco_infer: the model concatenates a global condition to the encoder outputs (:816-821): "
-                           "pk_taco_set_global_condition needs %d rows, got %d", B, condB);
+        PK_FAIL(PK_EINVAL, "%s: the model concatenates a global condition to the encoder outputs (:816-821): "
+                           "pk_taco_set_global_condition needs %d rows, got %d", fn, B, condB);
     h->inferred = false;
     h->B = B;
     h->T.assign(tok_lens, tok_lens + B);
     int maxT = 0;
     for (int b = 0; b < B; ++b) {
-        if (tok_lens[b] <= 0) PK_FAIL(PK_EINVAL, "pk_taco_infer: utterance %d has %d tokens", b, tok_lens[b]);
+        if (tok_lens[b] <= 0) PK_FAIL(PK_EINVAL, "%s: utterance %d has %d tokens", fn, b, tok_lens[b]);
         maxT = std::max(maxT, tok_lens[b]);
     }
     h->maxT = maxT;
     const int cap = max_decoder_steps;
     h->cap = cap;
+    const bool tf = teacher != nullptr;
+    long frames_total = 0;
+    std::vector<int> frm_off;
+    if (tf) {
+        frm_off.assign((size_t)B + 1, 0);
+        for (int b = 0; b < B; ++b) {
+            if (frame_lens[b] <= 0 || frame_lens[b] > cap) PK_FAIL(PK_EINVAL, "%s: utterance %d has %d teacher frames", fn, b, frame_lens[b]);
+            frames_total += frame_lens[b];
+            if (frames_total > 0x7fffffffL / std::max(M, Pn)) PK_FAIL(PK_EUNSUPPORTED, "%s: too many teacher frames", fn);
+            frm_off[b + 1] = (int)frames_total;
+        }
+    }
     // ---- encoder (:807-811)
     PK_TRY(pk_fft_build_timeline(ctx, h->tl_tok, tok_lens, B, h->gapr));
     Timeline& tl = h->tl_tok;
@@ -641,11 +777,11 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < tok_lens[b]; ++t, ++o) {
                 if (ids[o] < 0 || ids[o] >= c.vocab_size)
-                    PK_FAIL(PK_EINVAL, "pk_taco_infer: token id %lld out of [0,%d)", (long long)ids[o], c.vocab_size);
+                    PK_FAIL(PK_EINVAL, "%s: token id %lld out of [0,%d)", fn, (long long)ids[o], c.vocab_size);
                 tx[tl.seg_start[b] + t] = (int)ids[o];
                 if (tones) {
                     if (tones[o] < 0 || tones[o] >= c.n_tones)
-                        PK_FAIL(PK_EINVAL, "pk_taco_infer: tone id %lld out of [0,%d)", (long long)tones[o], c.n_tones);
+                        PK_FAIL(PK_EINVAL, "%s: tone id %lld out of [0,%d)", fn, (long long)tones[o], c.n_tones);
                     tn[tl.seg_start[b] + t] = (int)tones[o];
                 }
             }
@@ -744,9 +880,36 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
     const unsigned thr = pk_dropout_threshold((double)p);
     const float dscale = 1.0f / (1.0f - p);
     const size_t lsa_smem = (size_t)(8 + maxT + 4) * sizeof(float);
-    if (lsa_smem > 60 * 1024) PK_FAIL(PK_EUNSUPPORTED, "pk_taco_infer: %d tokens exceed the attention kernel's LDS budget", maxT);
+    if (lsa_smem > 60 * 1024) PK_FAIL(PK_EUNSUPPORTED, "%s: %d tokens exceed the attention kernel's LDS budget", fn, maxT);
     static const int poll = pk_prof_env("PK_TACO_POLL") ? std::max(1, atoi(pk_prof_env("PK_TACO_POLL"))) : 8;
     static const bool use_rg = pk_prof_env("PK_AR_ROWGEMM") ? atoi(pk_prof_env("PK_AR_ROWGEMM")) != 0 : true;
+    // both prenet layers in one launch (pk_ar.h k_ar_prenet_embed without the input layer)
+    const bool fused_prenet = use_rg && Pn % 4 == 0 && Pn / 4 <= 512 && 512 % (Pn / 4) == 0 && Pn <= 512 && M <= 512 && K1 % 4 == 0;
+    // ---- teacher forcing: every query row is known, the prenet runs once for all frames (k_taco_teacher_prenet); where the
+    // per-step prenet is not the kernel it mirrors, only the shifted query rows are built and the loop keeps its prenet
+    const float* tq = nullptr;   // position-major rows s * B + b: prenet outputs (fused_prenet) or queries
+    if (tf) {
+        if (M > 512) PK_FAIL(PK_EUNSUPPORTED, "%s: d_mels > 512", fn);
+        const float* d_teacher = teacher;
+        if (flags & PK_HOST_IO) {
+            PK_TRY(pk_upload(ctx, h->d_teacher, teacher, (size_t)frames_total * M * sizeof(float)));
+            d_teacher = h->d_teacher.as<float>();
+        }
+        PK_TRY(pk_upload(ctx, h->d_frmoff, frm_off.data(), frm_off.size() * sizeof(int)));
+        const int W = fused_prenet ? Pn : M;
+        PK_TRY(h->d_pre.reserve(((size_t)cap * B + SLACK) * W * sizeof(float)));
+        PK_HIP(hipMemsetAsync(h->d_pre.p, 0, (size_t)cap * B * W * sizeof(float), ctx->stream));   // steps past an utterance's L_b
+        TeacherPrenetArgs ta;
+        memset(&ta, 0, sizeof(ta));
+        ta.teacher = d_teacher; ta.frm_off = h->d_frmoff.as<int>(); ta.B = B; ta.M = M; ta.U = W; ta.total = (int)frames_total;
+        if (fused_prenet) {
+            ta.w1 = h->W(h->pre1_kn); ta.w2 = h->W(h->pre2_kn);
+        }
+        ta.out = h->d_pre.as<float>(); ta.ldo = W;
+        ta.dropout = drop ? 1 : 0; ta.seeds = d_seeds; ta.thr = thr; ta.scale = dscale;
+        PK_LAUNCH(ctx, "taco_teacher_prenet", k_taco_teacher_prenet, dim3(pk_div_up(frames_total, TP_R)), dim3(512), 0, ta);
+        tq = h->d_pre.as<float>();
+    }
     float* pq = pk_fft_act_ptr(h->d_pq, Da);
     // row GEMM of one of the per-step layers (B rows)
     // LSTMCell on the row GEMM: gates = [x | context | h] . [W_ih^T ; W_hh^T] + b, cell finished in the epilogue
@@ -771,13 +934,15 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
     int i = 0;
     for (i = 0; i < cap; ++i) {
         // query = prenet(previous mel_output) (:499-500, :538); the first query is zeros (:493-497)
-        const float* q = i == 0 ? zero : Y + (long)(i - 1) * B * M;
+        const float* q = tf ? tq + (long)i * B * M : i == 0 ? zero : Y + (long)(i - 1) * B * M;
         float* in1 = in1_[i & 1];          // this step's attention-LSTM operand rows
         float* in1n = in1_[(i & 1) ^ 1];   // the next step's: context(t) and attention_hidden(t) go there
         float* in2 = in2_[i & 1];
         float* in2n = in2_[(i & 1) ^ 1];
-        if (use_rg && Pn % 4 == 0 && Pn / 4 <= 512 && 512 % (Pn / 4) == 0 && Pn <= 512 && M <= 512 && K1 % 4 == 0) {
-            // both prenet layers in one launch (pk_ar.h k_ar_prenet_embed without the input layer)
+        if (tf && fused_prenet) {
+            PK_LAUNCH(ctx, "taco_prenet_rows", k_taco_prenet_rows, dim3(B), dim3(std::min(128, Pn / 4)), 0, tq + (long)i * B * Pn, Pn, in1, K1);
+            PK_TRY(rowlstm("taco_row_att_rnn", h->rw_att, in1, K1, h->d_catt.as<float>(), Ha, in1n + Pn + Eg, K1, in2, K2));
+        } else if (fused_prenet) {
             pk_prenet_embed pe;
             memset(&pe, 0, sizeof(pe));
             pe.y = q; pe.ldy = M; pe.O = M; pe.U = Pn; pe.A = Pn; pe.B = B;
@@ -831,11 +996,12 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
         }
         // linear_projection on [decoder_hidden | context] (:409-413) -> this step's mel row; stop rules (:515-528)
         if (use_rg && c.use_stop_token && B <= PK_RG_ROWS) {
-            // (one launch: the stop token rides on the projection's row GEMM as extra workgroups, pk_rowgemm.h stop_kind 1)
+            // (one launch: the stop token rides on the projection's row GEMM as extra workgroups, pk_rowgemm.h stop_kind 1;
+            // teacher forcing: stop_kind 2, the logit alone)
             pk_rowgemm_args g;
             g.x = in3; g.ldx = K3; g.Wt = h->W(h->rw_proj.w); g.bias = h->rw_proj.b == (size_t)-1 ? nullptr : h->W(h->rw_proj.b);
             g.y = Y + (long)i * B * M; g.ldy = M; g.M = B; g.K = h->rw_proj.K; g.N = h->rw_proj.N; g.act = PK_ACT_NONE;
-            g.stop_w = h->W(h->stop_w); g.stop_bias = h->stop_b; g.stop_kind = 1; g.stop_step = i; g.stop_max_steps = cap;
+            g.stop_w = h->W(h->stop_w); g.stop_bias = h->stop_b; g.stop_kind = tf ? 2 : 1; g.stop_step = i; g.stop_max_steps = cap;
             g.stop_probs = h->d_logits.as<float>(); g.stop_len = d_len; g.stop_ndone = d_ndone;
             PK_TRY(pk_rowgemm_launch(ctx, "taco_row_proj_stop", g));
         } else {
@@ -843,16 +1009,27 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
             PK_TRY(rowgemm("taco_row_proj", h->rw_proj, in3, K3, Y + (long)i * B * M, M, PK_ACT_NONE, -1, 0));
         else
             PK_TRY(pk_fft_run_dense(h, "taco_gemm_proj", h->proj, in3, K3, Y + (long)i * B * M, M, B, PK_ACT_NONE, nullptr, 0, nullptr));
+        if (!tf || c.use_stop_token)
         PK_LAUNCH(ctx, "taco_stop", k_taco_stop, dim3(pk_div_up(B, 4)), dim3(256), 0, in3, K3, K3,
                   c.use_stop_token ? h->W(h->stop_w) : (const float*)nullptr, h->stop_b, c.use_stop_token ? 1 : 0, B, i, cap,
-                  h->d_attw.as<float>(), tl.d_seg_start(), tl.d_seg_len(), h->d_logits.as<float>(), d_len, d_first, d_ndone);
+                  h->d_attw.as<float>(), tl.d_seg_start(), tl.d_seg_len(), h->d_logits.as<float>(), tf ? (int*)nullptr : d_len, d_first,
+                  d_ndone);
         }
-        if ((i + 1) % poll == 0 || i + 1 == cap) {
+        if (!tf && ((i + 1) % poll == 0 || i + 1 == cap)) {
             int ndone = 0;
             PK_HIP(hipMemcpyAsync(&ndone, d_ndone, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             PK_HIP(hipStreamSynchronize(ctx->stream));
             if (ndone >= B) break;
         }
+    }
+    if (tf) {
+        // the step count was known before the first launch: nothing was polled, the frames are the teacher's
+        h->steps = cap;
+        h->len.assign(frame_lens, frame_lens + B);
+        for (int b = 0; b < B; ++b) out_frames[b] = frame_lens[b];
+        PK_HIP(hipStreamSynchronize(ctx->stream));
+        h->inferred = true;
+        return PK_OK;
     }
     h->steps = std::min(i + 1, cap);
     h->len.resize(B);
@@ -860,17 +1037,39 @@ extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tone
     PK_HIP(hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < B; ++b) {
         if (h->len[b] <= 0 || h->len[b] > h->steps)
-            PK_FAIL(PK_EHIP, "pk_taco_infer: utterance %d did not stop within %d steps (internal error)", b, h->steps);
+            PK_FAIL(PK_EHIP, "%s: utterance %d did not stop within %d steps (internal error)", fn, b, h->steps);
         out_frames[b] = h->len[b];
     }
     h->inferred = true;
     return PK_OK;
 }
+}  // namespace
+
+extern "C" int pk_taco_infer(pk_taco* h, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
+                             int32_t max_decoder_steps, const uint64_t* seeds, int32_t flags, int32_t* out_frames) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_taco_infer: NULL argument");
+    return taco_run(h, "pk_taco_infer", ids, tones, tok_lens, B, max_decoder_steps, seeds, nullptr, nullptr, flags, out_frames);
+}
+
+extern "C" int pk_taco_teacher(pk_taco* h, const int64_t* ids, const int64_t* tones, const int32_t* tok_lens, int32_t B,
+                               const float* mels, const int32_t* frame_lens, const uint64_t* seeds, int32_t flags,
+                               int32_t* out_frames) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_taco_teacher: NULL argument");
+    int cap = 0;
+    if (mels && frame_lens)
+        for (int b = 0; b < B; ++b) cap = std::max(cap, frame_lens[b]);
+    if (!mels || !frame_lens || cap <= 0) {
+        h->cond_g.clear();   // the per-call conditioning is consumed by this call, whatever happens next
+        h->cond_B = 0;
+        PK_FAIL(PK_EINVAL, "pk_taco_teacher: teacher mels and positive frame lengths are required");
+    }
+    return taco_run(h, "pk_taco_teacher", ids, tones, tok_lens, B, cap, seeds, mels, frame_lens, flags, out_frames);
+}
 
 extern "C" int pk_taco_read(pk_taco* h, float* mel_output, float* mel_outputs_postnet, float* alignments,
                             float* stop_logits, int32_t flags) {
     if (!h) PK_FAIL(PK_EINVAL, "pk_taco_read: handle is NULL");
-    if (!h->inferred) PK_FAIL(PK_ESTATE, "pk_taco_read: call pk_taco_infer first");
+    if (!h->inferred) PK_FAIL(PK_ESTATE, "pk_taco_read: call pk_taco_infer or pk_taco_teacher first");
     if (stop_logits && !h->cfg.use_stop_token) PK_FAIL(PK_ESTATE, "pk_taco_read: the model has no stop token");
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
@@ -967,7 +1166,7 @@ extern "C" void pk_taco_destroy(pk_taco* h) {
     pk_dbuf* bufs[] = {&h->d_gc, &h->d_enc, &h->d_tok, &h->d_tone, &h->d_e1, &h->d_e2, &h->d_xg, &h->d_mem, &h->d_pkey, &h->d_attw, &h->d_cum,
                        &h->d_in1, &h->d_in1b, &h->d_in2, &h->d_in2b, &h->d_in3, &h->d_p1, &h->d_gates, &h->d_catt, &h->d_cdec, &h->d_zero, &h->d_y, &h->d_pq, &h->d_energy,
                        &h->d_logits, &h->d_state, &h->d_seeds, &h->d_align, &h->d_alignoff, &h->d_before, &h->d_q1,
-                       &h->d_q2, &h->d_rowmap, &h->d_stage, &h->d_stage2};
+                       &h->d_q2, &h->d_rowmap, &h->d_stage, &h->d_stage2, &h->d_teacher, &h->d_frmoff, &h->d_pre};
     for (auto* b : bufs) b->release();
     h->tl_tok.release();
     h->tl_frm.release();

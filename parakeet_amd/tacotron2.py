@@ -1,14 +1,17 @@
 """Tacotron2 acoustic model behind the reference's Python API.
 
 Mirrors parakeet/models/tacotron2.py: ``Tacotron2`` (constructor kwargs :626-649, ``set_state_dict``, ``eval``,
-``infer`` :781-840 -> dict of mel_output / mel_outputs_postnet / alignments [/ stop_logits]).  All arithmetic runs in
-libpk_synth.so (csrc/taco2.hip).  Training (``forward`` / loss) is out of scope; reduction_factor > 1 is refused (the
-reference's ``infer`` cannot run it either: the postnet gets the (B, T, d_mels * r) decoder output, :822-826).
+``infer`` :781-840 -> dict of mel_output / mel_outputs_postnet / alignments [/ stop_logits], ``forward`` :691-778 with
+eval semantics: the teacher-forced pass that ground-truth-aligned mels, scoring and alignment extraction need).  All
+arithmetic runs in libpk_synth.so (csrc/taco2.hip).  The loss and training-time dropout are out of scope;
+reduction_factor > 1 is refused (the reference's ``infer`` and ``forward`` cannot run it either: the postnet gets the
+(B, T, d_mels * r) decoder output, :822-826, :762).
 
 The decoder prenet keeps dropout on at inference (:76-79, training=True); the mask comes from the engine's
 counter-based dropout stream (include/pk_synth.h), selected by ``seed=``.
 
-Extension (superset): ``infer_batch`` decodes a ragged batch in lockstep, every utterance with its own stop.
+Extensions (superset): ``infer_batch`` decodes a ragged batch in lockstep, every utterance with its own stop;
+``teacher_forced_batch`` is ``forward`` for a ragged batch without padding.
 """
 import ctypes as C
 
@@ -83,9 +86,8 @@ class Tacotron2:
             _capi.check(self._ctx.lib.pk_taco_finalize(self._h))
             self._finalized = True
 
-    def infer_batch(self, texts, max_decoder_steps=1000, tones=None, seeds=None, global_condition=None):
-        """Lists of (T_b,) ids (and tone ids) -> list of dicts like ``infer`` returns, without the batch axis.
-        ``global_condition``: (B, d_global_condition), one row per utterance (:816-821)."""
+    def _pack(self, texts, tones, seeds, global_condition):
+        """The host arguments shared by pk_taco_infer and pk_taco_teacher; registers the global condition."""
         ctx = Context.get(self._ctx.device)
         self._finalize()
         if global_condition is not None:
@@ -107,13 +109,12 @@ class Tacotron2:
         if seeds is not None:
             sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
             assert sd.size == B, "one dropout seed per utterance"
-        frames = np.zeros(B, dtype=np.int32)
         i64p = C.POINTER(C.c_int64)
-        _capi.check(ctx.lib.pk_taco_infer(self._h, flat.ctypes.data_as(i64p),
-                                          None if tflat is None else tflat.ctypes.data_as(i64p),
-                                          lens.ctypes.data_as(C.POINTER(C.c_int32)), B, int(max_decoder_steps),
-                                          None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), 0,
-                                          frames.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (ctx, B, lens, flat.ctypes.data_as(i64p), None if tflat is None else tflat.ctypes.data_as(i64p),
+                None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), (flat, tflat, sd))
+
+    def _read(self, ctx, lens, frames):
+        """pk_taco_read of the last infer / teacher call -> list of dicts, one per utterance."""
         self._last_tok, self._last_frames = [int(v) for v in lens], [int(v) for v in frames]
         total = int(frames.sum())
         mel, post = ctx.empty((total, self.d_mels)), ctx.empty((total, self.d_mels))
@@ -131,6 +132,93 @@ class Tacotron2:
             o += L
             oa += L * T
         return outs
+
+    def infer_batch(self, texts, max_decoder_steps=1000, tones=None, seeds=None, global_condition=None):
+        """Lists of (T_b,) ids (and tone ids) -> list of dicts like ``infer`` returns, without the batch axis.
+        ``global_condition``: (B, d_global_condition), one row per utterance (:816-821)."""
+        ctx, B, lens, ids_p, tones_p, seeds_p, _keep = self._pack(texts, tones, seeds, global_condition)
+        frames = np.zeros(B, dtype=np.int32)
+        _capi.check(ctx.lib.pk_taco_infer(self._h, ids_p, tones_p, lens.ctypes.data_as(C.POINTER(C.c_int32)), B,
+                                          int(max_decoder_steps), seeds_p, 0, frames.ctypes.data_as(C.POINTER(C.c_int32))))
+        return self._read(ctx, lens, frames)
+
+    def teacher_forced_batch(self, texts, mels, tones=None, seeds=None, global_condition=None):
+        """The decoder teacher-forced on given mels (``Tacotron2Decoder.forward`` :419-472, eval semantics): lists of (T_b,)
+        ids and of (L_b, d_mels) frames in the model's own mel domain, L_b >= 1 -> list of dicts with the keys of
+        ``infer_batch``: mel_output (L_b, d_mels), mel_outputs_postnet, alignments (L_b, T_b) and, with a stop token,
+        stop_logits (L_b,).  The query of step s is frame s - 1 of ``mels`` (zeros for s = 0); the decoder runs exactly L_b
+        steps, a stop token ends nothing.  The prenet's dropout stays on, ``seeds`` as in ``infer_batch``: the teacher-forced
+        pass on ``infer_batch``'s own mel_output with the same seeds returns ``infer_batch``'s outputs bit for bit."""
+        if len(mels) != len(texts):
+            raise ValueError(f"{len(texts)} texts but {len(mels)} teacher mels")
+        dev = all(isinstance(m, torch.Tensor) and m.is_cuda for m in mels)
+        rows = [m.detach().to(torch.float32) if dev else to_numpy_f32(m) for m in mels]
+        for b, m in enumerate(rows):
+            if m.ndim != 2 or m.shape[1] != self.d_mels:
+                raise ValueError(f"teacher mel {b} has shape {tuple(m.shape)}, expected (L, {self.d_mels})")
+            if m.shape[0] < 1:
+                raise ValueError(f"teacher mel {b} is empty")
+        ctx, B, lens, ids_p, tones_p, seeds_p, _keep = self._pack(texts, tones, seeds, global_condition)
+        flens = np.array([m.shape[0] for m in rows], dtype=np.int32)
+        if dev:
+            packed = torch.cat(rows, dim=0).contiguous()
+            mel_p, flags = dptr(packed), 0
+        else:
+            packed = np.ascontiguousarray(np.concatenate(rows, axis=0))
+            mel_p, flags = _capi.fptr(packed), _capi.PK_HOST_IO
+        frames = np.zeros(B, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _capi.check(ctx.lib.pk_taco_teacher(self._h, ids_p, tones_p, lens.ctypes.data_as(i32p), B, mel_p,
+                                            flens.ctypes.data_as(i32p), seeds_p, flags, frames.ctypes.data_as(i32p)))
+        return self._read(ctx, lens, frames)
+
+    def forward(self, text_inputs, text_lens, mels, output_lens=None, tones=None, global_condition=None, seed=0):
+        """``Tacotron2.forward`` (:691-778) with eval semantics (like ``infer``: only the prenet's dropout is live, stream
+        ``seed + b`` for utterance b): text_inputs (B, T_text) padded ids, text_lens (B,), mels (B, T_mel, d_mels) padded,
+        output_lens (B,) or None (every utterance has T_mel frames), tones (B, T_text) ->
+        {"mel_output": (B, T_mel, d_mels), "mel_outputs_postnet": (B, T_mel, d_mels), "alignments": (B, T_mel, T_text),
+        "stop_logits": (B, T_mel) with a stop token}.
+
+        Every utterance is computed on its own text_lens[b] tokens and output_lens[b] frames; rows at or past output_lens[b]
+        (and alignment columns at or past text_lens[b]) are zero.  For B = 1 and for a batch of equal lengths this is what
+        the reference computes.  On a ragged padded batch the reference differs: its encoder convolutions are not masked
+        (:233-237), so padded token rows leak into the valid ones next to them; the postnet is applied before the output mask
+        (:762-769), so frames past output_lens[b] leak into the last valid ones; and it decodes the padded frames too, so its
+        alignments and stop logits past output_lens[b] are not zero."""
+        x = _ids(text_inputs)
+        if x.ndim == 1:
+            x = x[None]
+        B = x.shape[0]
+        tl = _ids(text_lens).reshape(-1)
+        m = mels if isinstance(mels, torch.Tensor) and mels.is_cuda else to_numpy_f32(mels)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[0] != B or tl.size != B:
+            raise ValueError(f"forward: {B} texts, {tl.size} text_lens, mels of shape {tuple(m.shape)}")
+        T_mel = int(m.shape[1])
+        ol = np.full(B, T_mel, dtype=np.int64) if output_lens is None else _ids(output_lens).reshape(-1)
+        if ol.size != B or (ol < 1).any() or (ol > T_mel).any() or (tl < 1).any() or (tl > x.shape[1]).any():
+            raise ValueError("forward: text_lens / output_lens out of range")
+        tn = None
+        if tones is not None:
+            tn = _ids(tones).reshape(B, -1)
+            tn = [tn[b, :tl[b]] for b in range(B)]
+        outs = self.teacher_forced_batch([x[b, :tl[b]] for b in range(B)], [m[b, :ol[b]] for b in range(B)], tones=tn,
+                                         seeds=[int(seed) + b for b in range(B)], global_condition=global_condition)
+        ctx = Context.get(self._ctx.device)
+        res = {"mel_output": torch.zeros((B, T_mel, self.d_mels), device=ctx.device),
+               "mel_outputs_postnet": torch.zeros((B, T_mel, self.d_mels), device=ctx.device),
+               "alignments": torch.zeros((B, T_mel, x.shape[1]), device=ctx.device)}
+        if self.use_stop_token:
+            res["stop_logits"] = torch.zeros((B, T_mel), device=ctx.device)
+        for b, o in enumerate(outs):
+            L, T = int(ol[b]), int(tl[b])
+            res["mel_output"][b, :L] = o["mel_output"]
+            res["mel_outputs_postnet"][b, :L] = o["mel_outputs_postnet"]
+            res["alignments"][b, :L, :T] = o["alignments"]
+            if self.use_stop_token:
+                res["stop_logits"][b, :L] = o["stop_logits"]
+        return {k: wrap(v) for k, v in res.items()}
 
     def infer(self, text_inputs, max_decoder_steps=1000, tones=None, global_condition=None, seed=0):
         """text_inputs (1, T) [or (T,)] int64 -> {"mel_output": (1, L, C), "mel_outputs_postnet": (1, L, C),
