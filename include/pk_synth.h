@@ -14,7 +14,7 @@
  *               FastSpeech2.__init__ :52-296, inference :468-558
  *               (_forward(is_inference=True) :377-466),
  *               FastSpeech2Inference.forward :668-671
- *   pk_wf_*     parakeet/models/waveflow.py ConditionalWaveFlow.infer :785-805
+ *   pk_wf_*     parakeet/models/waveflow.py ConditionalWaveFlow.infer :785-805, forward :759-782
  *   pk_tts_*    parakeet/models/transformer_tts/transformer_tts.py TransformerTTS.inference :511-647,
  *               TransformerTTSInference.forward :757-767
  *   pk_taco_*   parakeet/models/tacotron2.py Tacotron2.infer :781-840 (Tacotron2Decoder.infer :474-541),
@@ -361,6 +361,18 @@ int pk_wf_cond_length(pk_wf* h, int32_t t_mel, int32_t* cond_len, int32_t* wav_l
  *   wav    packed output, wav_len(frames[b]) floats per utterance */
 int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, int32_t B, const float* z,
                 float* wav, int32_t flags);
+/* ConditionalWaveFlow.forward (:759-782): density estimation, audio -> (z, log-determinant), for a packed ragged batch.  Not
+ * autoregressive: a layer of a flow runs on all n_group - 1 rows in one launch (n_flows x n_layers dependent layer launches).
+ *   mel, frames  as pk_wf_infer (frames >= 1); the condition is the UNTRIMMED upsampled mel (:780), frames[b] * prod(factors) long
+ *   audio        packed, audio_len[b] floats per utterance; n_group <= audio_len[b] <= frames[b] * prod(factors) (_trim :617-625),
+ *                else PK_EINVAL
+ *   z            packed output, audio_len[b] / n_group * n_group floats per utterance (pk_wf_forward_length)
+ *   logdet       (B) DOUBLE: sum of logs over the flows, rows and positions of utterance b (the reference returns their sum over the
+ *                batch, :671).  Fixed summation order: the same bits for an utterance in any batch, as z.
+ * Pointers are device memory, or host with PK_HOST_IO (frames / audio_len are always host).  PK_ESTATE before pk_wf_finalize. */
+int pk_wf_forward_length(pk_wf* h, int32_t t_mel, int32_t n_audio, int32_t* z_len);
+int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, const float* audio, const int32_t* audio_len, int32_t B,
+                  float* z, double* logdet, int32_t flags);
 void pk_wf_destroy(pk_wf* h);
 
 /* ------------------------------------------------------------ SpeedySpeech */

@@ -154,6 +154,8 @@ def _declare(lib):
         "pk_wf_finalize": (C.c_int, [vp]),
         "pk_wf_cond_length": (C.c_int, [vp, i32, i32p, i32p]),
         "pk_wf_infer": (C.c_int, [vp, f32p, i32p, i32, f32p, f32p, i32]),
+        "pk_wf_forward_length": (C.c_int, [vp, i32, i32, i32p]),
+        "pk_wf_forward": (C.c_int, [vp, f32p, i32p, f32p, i32p, i32, f32p, C.c_void_p, i32]),
         "pk_wf_destroy": (None, [vp]),
         "pk_ss_create": (C.c_int, [vp, C.POINTER(SsCfg), C.POINTER(vp)]),
         "pk_ss_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),

@@ -128,3 +128,15 @@ int wfl_cond_planes_launch(pk_ctx* ctx, float* cond, long row_stride, int rows, 
 int wfl_step_launch(pk_ctx* ctx, int C, const float* prm, float b_logs, float b_b, const float* z_row,
                     float* x_row, const float* w_in, const float* b_in, float* h0_next, unsigned* h0_amax,
                     const int* pos_utt, int npos_alloc, int first);
+
+// ---- the forward direction (pk_wf_forward): the rows of a flow as "flat" rows, one behind the other on one position axis, so that
+// ONE wfl_layer_launch covers every (row, 32-position tile) of a layer: slot_stride = the positions of a row * C, tap_slot = the
+// kernel row, npos_alloc = rows * positions of a row, in0 = a buffer that starts with two rows of zeros (the rows before the first).
+constexpr int WFL_MAX_ROWS = 16;
+struct WflRowMap { int row[WFL_MAX_ROWS]; };
+// dst row r (planes, block maxima in amax) = src row map.row[r] (fp32 [pos / 32][96][32]); channel n_mels := 1 (see above)
+int wfl_cond_planes_rows_launch(pk_ctx* ctx, const float* src, long src_row_stride, float* dst, long dst_row_stride, unsigned* amax,
+                                long amax_row_stride, const WflRowMap& map, int rows, int nblk, int n_mels);
+// h0[row] = input_proj(x[row]) for rows 0 .. rows-1 as planes with block maxima (strides in floats / blocks)
+int wfl_inproj_rows_launch(pk_ctx* ctx, int C, const float* x, long x_row_stride, const float* w_in, const float* b_in, float* h0,
+                           long h0_row_stride, unsigned* h0_amax, long amax_row_stride, const int* pos_utt, int npos_alloc, int rows);

@@ -39,10 +39,11 @@ __global__ void k_wf_upsample(const float* __restrict__ in, const int* __restric
                               const int* __restrict__ in_len, float* __restrict__ out,
                               const int* __restrict__ out_off, const float* __restrict__ w, float bias, int f,
                               int M, int fold_G, const int* __restrict__ woff, const int* __restrict__ pruned,
-                              long cond_row_stride, int cond_ld, int blocked) {
+                              long cond_row_stride, int cond_ld, int blocked, int trim) {
     const int b = blockIdx.z;
     const int Tin = in_len[b];
-    const int Tout = f * Tin - f;  // (Tin-1)*f - 2*(f/2) + 2f, minus the trimmed (2f - f) columns
+    // (Tin-1)*f - 2*(f/2) + 2f = f*Tin columns; infer trims the last 2f - f of them (trim_conv_artifact :124-127), forward keeps them (:780)
+    const int Tout = trim ? f * Tin - f : f * Tin;
     const int t = blockIdx.x * (blockDim.x / M) + threadIdx.x / M;
     const int c = threadIdx.x % M;
     if (t >= Tout || threadIdx.x >= (blockDim.x / M) * M) return;
@@ -133,6 +134,99 @@ __global__ __launch_bounds__(256) void k_wf_step(const float* __restrict__ skips
         for (int c = lane; c < C; c += 64) h0_next[(long)p * C + c] = valid ? fmaf(w_in[c], xn, b_in[c]) : 0.f;
 }
 
+// ---- the forward direction (Flow.forward :465-494): small kernels around the layers.  Rows are "flat" (pk_wf_layer.h): row r of a
+// per-row buffer sits at positions [r * npos_alloc, (r + 1) * npos_alloc).
+struct WfRowMap { int row[WFL_MAX_ROWS]; };
+
+// z' = shuffle(Flow._transform(x), perm): z[0] = x[0], z[r] = x[r] exp(logs[r-1]) + b[r-1] (:459-463), (logs, b) = prm + the biases;
+// row r goes to row dst.row[r] of nxt (geo.shuffle_dim :664 as an index map).  Gap positions -> 0.
+__global__ void k_wf_affine_rows(const float* __restrict__ x, float* __restrict__ nxt, long x_row_stride,
+                                 const float* __restrict__ prm, long prm_row, float b_logs, float b_b,
+                                 const int* __restrict__ pos_utt, int npos, WfRowMap dst) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (p >= npos) return;
+    float v = 0.f;
+    if (pos_utt[p] >= 0) {
+        v = x[(long)r * x_row_stride + p];
+        if (r > 0) {
+            const float2 lb = reinterpret_cast<const float2*>(prm)[(long)(r - 1) * prm_row + p];
+            v = v * expf(lb.x + b_logs) + (lb.y + b_b);
+        }
+    }
+    nxt[(long)dst.row[r] * x_row_stride + p] = v;
+}
+
+// sum of logs over 256 positions of ONE utterance and one row, in a fixed order and in double: part[poff[b] + r * nch[b] + c].  The
+// chunks are cut per utterance, so an utterance's partial sums do not depend on what else is in the batch.
+__global__ __launch_bounds__(256) void k_wf_logs_partial(const float* __restrict__ prm, long prm_row, float b_logs,
+                                                         const int* __restrict__ woff, const int* __restrict__ wlen,
+                                                         const int* __restrict__ nch, const int* __restrict__ poff,
+                                                         double* __restrict__ part) {
+    const int c = blockIdx.x, r = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    if (c >= nch[b]) return;
+    const int w = c * 256 + t;
+    __shared__ double s[256];
+    s[t] = w < wlen[b] ? (double)(prm[2 * ((long)r * prm_row + woff[b] + w)] + b_logs) : 0.0;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) s[t] += s[t + o];
+        __syncthreads();
+    }
+    if (t == 0) part[(long)poff[b] + (long)r * nch[b] + c] = s[0];
+}
+
+// logdet[b] (+)= the utterance's partial sums of one flow, fixed order, double
+__global__ __launch_bounds__(64) void k_wf_logdet_acc(const double* __restrict__ part, const int* __restrict__ nch,
+                                                      const int* __restrict__ poff, int rows, double* __restrict__ logdet, int first) {
+    const int b = blockIdx.x, t = threadIdx.x, n = rows * nch[b];
+    __shared__ double s[64];
+    double a = 0.0;
+    for (int i = t; i < n; i += 64) a += part[(long)poff[b] + i];
+    s[t] = a;
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) {
+        if (t < o) s[t] += s[t + o];
+        __syncthreads();
+    }
+    if (t == 0) logdet[b] = (first ? 0.0 : logdet[b]) + s[0];
+}
+
+// unfused path: h0[p][C] = input_proj(x) for every flat position (row = p / npos_alloc)
+__global__ void k_wf_inproj_rows_f32(const float* __restrict__ x, long x_row_stride, const float* __restrict__ w_in,
+                                     const float* __restrict__ b_in, float* __restrict__ h0, const int* __restrict__ pos_utt_flat,
+                                     int npos_alloc, long total, int C) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long p = i / C;
+    const int c = (int)(i % C);
+    const float xv = x[(p / npos_alloc) * x_row_stride + p % npos_alloc];
+    h0[i] = pos_utt_flat[p] >= 0 ? fmaf(w_in[c], xv, b_in[c]) : 0.f;
+}
+
+// unfused path: prm[p] = output_proj(sum of skips) without its bias (:455-456); one wave per flat position
+__global__ __launch_bounds__(256) void k_wf_params_rows(const float* __restrict__ skipsum, int C, const float* __restrict__ w_out,
+                                                        float* __restrict__ prm, long total) {
+    const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= total) return;
+    const int lane = threadIdx.x & 63;
+    const float* s = skipsum + p * C;
+    float l = 0.f, bb = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float v = s[c];
+        l = fmaf(w_out[c], v, l);
+        bb = fmaf(w_out[C + c], v, bb);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        l += __shfl_xor(l, o);
+        bb += __shfl_xor(bb, o);
+    }
+    if (lane == 0) {
+        prm[2 * p] = l;
+        prm[2 * p + 1] = bb;
+    }
+}
+
 }  // namespace
 
 // ================================================================== host side
@@ -175,6 +269,7 @@ struct pk_wf {
     std::vector<float> up_b;
     // workspace
     pk_dbuf ws_tab, ws_mel, ws_z, ws_wav, ws_u[2], ws_cond, ws_cur, ws_nxt, ws_hist, ws_zbuf, ws_skip, ws_hamax, ws_camax, ws_trace, ws_bar, ws_desc, ws_replay;
+    pk_dbuf ws_fa, ws_fb, ws_fam, ws_fcond, ws_fcam, ws_fprm, ws_fpart, ws_flogdet, ws_fz, ws_fskip;   // pk_wf_forward
     std::vector<WflLayer> desc_host;   // host image of ws_desc (kept until the next inference: the upload is asynchronous)
     const float* W(size_t off) const { return arena.as<float>() + off; }
 };
@@ -562,7 +657,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
             dim3 grid(pk_div_up(maxT, tpb), 1, B);
             PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(256), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i],
                       out, d_tab + o_outoff[i], h->W(h->up_w[i]), h->up_b[i], f, M, last ? G : 0, d_tab + o_woff,
-                      d_tab + o_pruned, cond_row, MP, use_wfl ? 1 : 0);
+                      d_tab + o_pruned, cond_row, MP, use_wfl ? 1 : 0, 1);
             in = out;
         }
     }
@@ -888,13 +983,358 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     return PK_OK;
 }
 
+// ================================================================== forward (density estimation)
+static long wf_hop(const pk_wf_cfg& c) {
+    long hop = 1;
+    for (int i = 0; i < c.n_upsample; ++i) hop *= c.upsample_factors[i];
+    return hop;
+}
+
+extern "C" int pk_wf_forward_length(pk_wf* h, int32_t t_mel, int32_t n_audio, int32_t* z_len) {
+    if (!h || !z_len) PK_FAIL(PK_EINVAL, "pk_wf_forward_length: NULL argument");
+    if (t_mel < 1) PK_FAIL(PK_EINVAL, "pk_wf_forward_length: %d mel frames", t_mel);
+    if (n_audio < h->cfg.n_group || n_audio > (long)t_mel * wf_hop(h->cfg))   // _trim :618: the condition covers the audio
+        PK_FAIL(PK_EINVAL, "pk_wf_forward_length: %d samples for %d frames (n_group %d .. %ld)", n_audio, t_mel, h->cfg.n_group,
+                (long)t_mel * wf_hop(h->cfg));
+    *z_len = n_audio / h->cfg.n_group * h->cfg.n_group;
+    return PK_OK;
+}
+
+// ConditionalWaveFlow.forward :759-782 = UpsampleNet (untrimmed, :780) + WaveFlow.forward :627-672.  Every row of the folded audio is
+// known, so Flow.forward (:491-493) runs the ResidualNet on rows 0 .. G-2 with condition rows 1 .. G-1 AT ONCE: the rows of a flow
+// lie one behind the other on one position axis ("flat" rows) behind two rows of zeros (the rows before the first: the causal
+// (3, 3) conv's padding in height, :229-236), and a layer of a flow is ONE launch of the fused layer kernel over all G - 1 rows
+// with all nine taps -- n_flows x n_layers dependent layer launches per call instead of infer's n_flows x (G - 1) x n_layers.
+// Two such buffers, ping-ponged between the layers (a layer reads positions other workgroups write).
+// Utterances start at multiples of 32 positions with at least 192 gap positions between them: the 32-position scale blocks then
+// fall at the same places inside an utterance, and no tile of one utterance reads a block of another, whatever else is in the
+// batch -- z and logdet of an utterance are the same bit for bit in any batch.
+extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, const float* audio, const int32_t* audio_len,
+                             int32_t B, float* z, double* logdet, int32_t flags) {
+    if (!h || !mel || !frames || !audio || !audio_len || !z || !logdet) PK_FAIL(PK_EINVAL, "pk_wf_forward: NULL argument");
+    if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_wf_forward: call pk_wf_finalize first");
+    if (B <= 0) PK_FAIL(PK_EINVAL, "pk_wf_forward: batch size must be positive");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const pk_wf_cfg& c = h->cfg;
+    const int C = c.channels, M = c.n_mels, G = c.n_group, NL = c.n_layers, MP = h->mp, R = G - 1;
+    const long hop = wf_hop(c);
+    constexpr int FGAP = 192, CHUNK = 256;
+    // ---- per-utterance sizes
+    std::vector<int> cuT(B + 1, 0), pruned(B), Wb(B), woff(B), aoff(B), ooff(B), nch(B), poff(B);
+    long sumA = 0, sumO = 0, sumP = 0, pos = h->gapw;
+    int max_nch = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1) PK_FAIL(PK_EINVAL, "pk_wf_forward: utterance %d has no mel frames", b);
+        if (audio_len[b] < G) PK_FAIL(PK_EINVAL, "pk_wf_forward: utterance %d has %d samples, fewer than n_group %d", b, audio_len[b], G);
+        if (audio_len[b] > frames[b] * hop)
+            PK_FAIL(PK_EINVAL, "pk_wf_forward: utterance %d has %d samples but its %d frames cover %ld (the condition must cover the audio)", b,
+                    audio_len[b], frames[b], frames[b] * hop);
+        cuT[b + 1] = cuT[b] + frames[b];
+        pruned[b] = audio_len[b] / G * G;
+        Wb[b] = pruned[b] / G;
+        woff[b] = (int)pos;
+        pos = (pos + Wb[b] + 31) / 32 * 32 + FGAP;
+        aoff[b] = (int)sumA;
+        ooff[b] = (int)sumO;
+        nch[b] = (Wb[b] + CHUNK - 1) / CHUNK;
+        poff[b] = (int)sumP;
+        max_nch = std::max(max_nch, nch[b]);
+        sumA += audio_len[b];
+        sumO += pruned[b];
+        sumP += (long)R * nch[b];
+    }
+    const long npos_l = (pos + PK_GEMM_BM - 1) / PK_GEMM_BM * PK_GEMM_BM;
+    if (npos_l * R >= (1L << 31) - 4096 || sumA >= (1L << 31)) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_forward: %ld positions per row are too many for one call; split the batch", npos_l);
+    const int npos = (int)pos, npos_alloc = (int)npos_l;
+    const long pstride = (long)npos_alloc + 2 * WF_LEAD;
+    const long nflat = (long)R * npos_alloc;        // positions of the flat rows of one flow
+    const int nblk = npos_alloc / WFL_BLK;
+    // ---- tables
+    std::vector<int> pos_utt((size_t)nflat, -1), pos_w(npos_alloc, 0);
+    for (int b = 0; b < B; ++b)
+        for (int w = 0; w < Wb[b]; ++w) {
+            pos_utt[woff[b] + w] = b;
+            pos_w[woff[b] + w] = w;
+        }
+    for (int r = 1; r < R; ++r) std::copy(pos_utt.begin(), pos_utt.begin() + npos_alloc, pos_utt.begin() + (size_t)r * npos_alloc);
+    std::vector<int> tab;
+    auto push = [&](const std::vector<int>& v) {
+        size_t o = tab.size();
+        tab.insert(tab.end(), v.begin(), v.end());
+        return o;
+    };
+    const size_t o_putt = push(pos_utt), o_pw = push(pos_w), o_woff = push(woff), o_aoff = push(aoff), o_ooff = push(ooff),
+                 o_pruned = push(pruned), o_wlen = push(Wb), o_nch = push(nch), o_poff = push(poff);
+    std::vector<size_t> o_inoff(c.n_upsample), o_inlen(c.n_upsample), o_outoff(c.n_upsample);
+    std::vector<long> layer_rows(c.n_upsample + 1);
+    std::vector<int> up_maxT(c.n_upsample, 0);
+    {
+        std::vector<int> len(frames, frames + B), off(cuT.begin(), cuT.begin() + B);
+        layer_rows[0] = cuT[B];
+        for (int i = 0; i < c.n_upsample; ++i) {
+            const int f = c.upsample_factors[i];
+            std::vector<int> olen(B), ooff2(B);
+            long acc = 0;
+            for (int b = 0; b < B; ++b) {
+                olen[b] = f * len[b];   // untrimmed
+                ooff2[b] = (int)acc;
+                acc += olen[b];
+                up_maxT[i] = std::max(up_maxT[i], olen[b]);
+            }
+            if (acc >= (1L << 31)) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_forward: the batch is too long for one call; split it");
+            o_inoff[i] = push(off);
+            o_inlen[i] = push(len);
+            o_outoff[i] = push(ooff2);
+            layer_rows[i + 1] = acc;
+            len = olen;
+            off = ooff2;
+        }
+    }
+    PK_TRY(h->ws_tab.reserve(tab.size() * sizeof(int)));
+    PK_HIP(hipMemcpyAsync(h->ws_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    PK_HIP(hipStreamSynchronize(ctx->stream));
+    const int* d_tab = h->ws_tab.as<int>();
+    const int* putt_flat = d_tab + o_putt;   // its first npos_alloc entries are the table of one row
+
+    // ---- io staging
+    const float* d_mel = mel;
+    const float* d_audio = audio;
+    float* d_z = z;
+    PK_TRY(h->ws_flogdet.reserve((size_t)B * sizeof(double)));
+    double* d_logdet = (flags & PK_HOST_IO) ? h->ws_flogdet.as<double>() : logdet;
+    if (flags & PK_HOST_IO) {
+        PK_TRY(h->ws_mel.reserve((size_t)cuT[B] * M * 4));
+        PK_TRY(h->ws_z.reserve((size_t)sumA * 4));
+        PK_TRY(h->ws_wav.reserve((size_t)sumO * 4));
+        PK_HIP(hipMemcpyAsync(h->ws_mel.p, mel, (size_t)cuT[B] * M * 4, hipMemcpyHostToDevice, ctx->stream));
+        PK_HIP(hipMemcpyAsync(h->ws_z.p, audio, (size_t)sumA * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_mel = h->ws_mel.as<float>();
+        d_audio = h->ws_z.as<float>();
+        d_z = h->ws_wav.as<float>();
+    }
+    // ---- workspaces
+    const bool use_wfl = wfl_usable(h) && (h->math == PK_GEMM_MATH_F16X3 || h->math == PK_GEMM_MATH_F16);
+    const long cond_row = pstride * MP;                      // floats per folded cond row as the upsampler writes it
+    const long frow = (long)npos_alloc * C;                  // floats per flat feature row
+    const size_t feat_bytes = ((size_t)(R + 2) * frow + 2 * (size_t)WF_LEAD * C) * 4;   // two zero rows + R rows + margins
+    const size_t fcond_bytes = ((size_t)nflat + 2 * WF_LEAD) * MP * 4;
+    const long am_rows = (long)(R + 2) * nblk + 2 * (WF_LEAD / WFL_BLK);   // block maxima of one feature buffer incl. margins
+    PK_TRY(h->ws_cond.reserve((size_t)G * cond_row * 4));
+    PK_TRY(h->ws_cur.reserve((size_t)G * pstride * 4));
+    PK_TRY(h->ws_nxt.reserve((size_t)G * pstride * 4));
+    PK_TRY(h->ws_fa.reserve(feat_bytes));
+    PK_TRY(h->ws_fb.reserve(feat_bytes));
+    PK_TRY(h->ws_fcond.reserve(fcond_bytes));
+    PK_TRY(h->ws_fprm.reserve((size_t)nflat * 2 * 4));
+    PK_TRY(h->ws_fpart.reserve((size_t)sumP * sizeof(double)));
+    for (int i = 0; i + 1 < c.n_upsample; ++i) PK_TRY(h->ws_u[i & 1].reserve((size_t)layer_rows[i + 1] * M * 4));
+    PK_HIP(hipMemsetAsync(h->ws_cond.p, 0, (size_t)G * cond_row * 4, ctx->stream));
+    PK_HIP(hipMemsetAsync(h->ws_fa.p, 0, feat_bytes, ctx->stream));      // the zero rows and the margins stay zero
+    PK_HIP(hipMemsetAsync(h->ws_fb.p, 0, feat_bytes, ctx->stream));
+    PK_HIP(hipMemsetAsync(h->ws_fcond.p, 0, fcond_bytes, ctx->stream));
+    if (use_wfl) {
+        PK_TRY(h->ws_fam.reserve((size_t)2 * am_rows * 4));
+        PK_TRY(h->ws_fcam.reserve(((size_t)R * nblk + 2 * (WF_LEAD / WFL_BLK)) * 4));
+        PK_HIP(hipMemsetAsync(h->ws_fam.p, 0, (size_t)2 * am_rows * 4, ctx->stream));
+        PK_HIP(hipMemsetAsync(h->ws_fcam.p, 0, ((size_t)R * nblk + 2 * (WF_LEAD / WFL_BLK)) * 4, ctx->stream));
+    } else {
+        PK_TRY(h->ws_fz.reserve(((size_t)nflat + 2 * WF_LEAD) * C * 4));
+        PK_TRY(h->ws_fskip.reserve(((size_t)nflat + 2 * WF_LEAD) * C * 4));
+        PK_HIP(hipMemsetAsync(h->ws_fz.p, 0, ((size_t)nflat + 2 * WF_LEAD) * C * 4, ctx->stream));
+    }
+    float* cond = h->ws_cond.as<float>() + (size_t)WF_LEAD * MP;
+    float* cur = h->ws_cur.as<float>() + WF_LEAD;
+    float* nxt = h->ws_nxt.as<float>() + WF_LEAD;
+    float* fbuf[2] = {h->ws_fa.as<float>() + (size_t)WF_LEAD * C, h->ws_fb.as<float>() + (size_t)WF_LEAD * C};   // row 0 of each = zeros
+    unsigned* fam[2] = {nullptr, nullptr};
+    if (use_wfl) {
+        fam[0] = h->ws_fam.as<unsigned>() + WF_LEAD / WFL_BLK;
+        fam[1] = fam[0] + am_rows;
+    }
+    float* fcond = h->ws_fcond.as<float>() + (size_t)WF_LEAD * MP;
+    unsigned* fcam = use_wfl ? h->ws_fcam.as<unsigned>() + WF_LEAD / WFL_BLK : nullptr;
+    float* prm = h->ws_fprm.as<float>();
+    double* part = h->ws_fpart.as<double>();
+
+    // ---- upsample (encoder), untrimmed; the last layer writes the folded rows (only the samples the audio covers, _trim :623-624)
+    {
+        const float* in = d_mel;
+        for (int i = 0; i < c.n_upsample; ++i) {
+            const int f = c.upsample_factors[i];
+            const bool last = i == c.n_upsample - 1;
+            float* out = last ? cond : h->ws_u[i & 1].as<float>();
+            const int tpb = 256 / M;
+            dim3 grid(pk_div_up(up_maxT[i], tpb), 1, B);
+            PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(256), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i], out,
+                      d_tab + o_outoff[i], h->W(h->up_w[i]), h->up_b[i], f, M, last ? G : 0, d_tab + o_woff, d_tab + o_pruned,
+                      cond_row, MP, use_wfl ? 1 : 0, 0);
+            in = out;
+        }
+    }
+    // ---- fold the audio (:653-654)
+    PK_LAUNCH(ctx, "wf_fold", k_wf_fold, dim3(pk_div_up(npos, 256)), dim3(256), 0, d_audio, putt_flat, d_tab + o_pw, d_tab + o_aoff,
+              G, npos, pstride, cur);
+
+    // ---- flows (:660-665)
+    std::vector<int> cidx(G);
+    for (int i = 0; i < G; ++i) cidx[i] = i;
+    const bool split_math = h->math == PK_GEMM_MATH_F16X3;
+    (void)split_math;
+    for (int fl = 0; fl < c.n_flows; ++fl) {
+        const WfFlowW& F = h->flows[fl];
+        std::vector<int> perm(G), inv(G);   // _create_perm :602-615
+        for (int i = 0; i < G; ++i)
+            perm[i] = (fl < c.n_flows / 2) ? (G - 1 - i) : (i < G / 2 ? G / 2 - 1 - i : G + G / 2 - 1 - i);
+        for (int i = 0; i < G; ++i) inv[perm[i]] = i;
+        float b_logs = F.b_logs, b_b = F.b_b;
+        if (use_wfl) {
+            // the condition rows 1 .. G-1 in this flow's (cumulatively shuffled) order, as planes
+            WflRowMap cm;
+            memset(&cm, 0, sizeof(cm));
+            for (int r = 0; r < R; ++r) cm.row[r] = cidx[r + 1];
+            PK_TRY(wfl_cond_planes_rows_launch(ctx, cond, cond_row, fcond, (long)npos_alloc * MP, fcam, nblk, cm, R, nblk, M));
+            // layer 0's input: input_proj of the rows 0 .. G-2 behind the two zero rows
+            PK_TRY(wfl_inproj_rows_launch(ctx, C, cur, pstride, h->W(F.w_in), h->W(F.b_in), fbuf[0] + 2 * frow, frow, fam[0] + 2 * nblk, nblk,
+                                          putt_flat, npos_alloc, R));
+            for (int l = 0; l < NL; ++l) {
+                const WfLayerW& L = F.layers[l];
+                const int in = l & 1, out = in ^ 1;
+                WflLaunch w;
+                memset(&w, 0, sizeof(w));
+                w.C = C;
+                w.f16 = h->math == PK_GEMM_MATH_F16;
+                w.slot_stride = frow;          // "ring slot" kr of a tile = the row kr - 2 rows before the tile's own
+                w.amax_stride = nblk;
+                w.cur_slot = 2;
+                w.prm = prm;
+                w.cond = fcond;
+                w.cond_amax = fcam;
+                w.ntap = 9;
+                for (int t = 0; t < 9; ++t) {
+                    w.tap_slot[t] = t / 3;
+                    w.tap_col[t] = t % 3 - 1;
+                    w.tap_w[t] = t;
+                }
+                w.pos_utt = putt_flat;
+                w.npos_alloc = (int)nflat;
+                w.waves = h->layer_waves;
+                w.nl = 1;
+                w.l0.w.w1 = h->arena16.as<uint16_t>() + L.fl.w1;
+                w.l0.w.w2 = h->arena16.as<uint16_t>() + L.fl.w2;
+                w.l0.w.b2r = h->W(L.fl.b2r);
+                w.l0.w.wso = h->W(L.fl.wso);
+                w.l0.w.k1 = L.fl.k1;
+                w.l0.w.k2res = L.fl.k2res;
+                w.l0.in0 = fbuf[in];
+                w.l0.in_amax0 = fam[in];
+                w.l0.out = l + 1 < NL ? fbuf[out] + 2 * frow : nullptr;   // the last layer's residual output is unused (:390)
+                w.l0.out_amax = l + 1 < NL ? fam[out] + 2 * nblk : nullptr;
+                w.l0.first = l == 0;
+                w.l0.dil = 1 << l;
+                PK_TRY(wfl_layer_launch(ctx, w));
+            }
+            b_logs = F.b_logs_f;
+            b_b = F.b_b_f;
+        } else {
+            // the unfused path (any width / n_mels, exact-fp32 math): the same flat rows as [pos][C] fp32 through the GEMM kernels
+            float* zbuf = h->ws_fz.as<float>() + (size_t)WF_LEAD * C;
+            float* skip = h->ws_fskip.as<float>() + (size_t)WF_LEAD * C;
+            for (int r = 0; r < R; ++r)
+                PK_HIP(hipMemcpyAsync(fcond + (size_t)r * npos_alloc * MP, cond + (size_t)cidx[r + 1] * cond_row, (size_t)npos_alloc * MP * 4,
+                                      hipMemcpyDeviceToDevice, ctx->stream));
+            PK_LAUNCH(ctx, "wf_inproj_rows", k_wf_inproj_rows_f32, dim3(pk_div_up(nflat * C, 256)), dim3(256), 0, cur, pstride, h->W(F.w_in),
+                      h->W(F.b_in), fbuf[0] + 2 * frow, putt_flat, npos_alloc, nflat * C, C);
+            for (int l = 0; l < NL; ++l) {
+                const WfLayerW& L = F.layers[l];
+                float* in = fbuf[l & 1] + 2 * frow;    // row r of the layer input (rows r - 2, r - 1 in front of it)
+                float* out = fbuf[(l & 1) ^ 1] + 2 * frow;
+                pk_gemm_args g;
+                g.A = in;
+                g.lda = C;
+                g.Cin = C;
+                g.ntaps = 0;
+                const long dil = 1L << l;
+                for (int kr = 0; kr < 3; ++kr)
+                    for (int kc = 0; kc < 3; ++kc) {
+                        g.tap_off[g.ntaps] = (long)(kr - 2) * frow + (long)(kc - 1) * dil * C;
+                        g.tap_w[g.ntaps] = kr * 3 + kc;
+                        ++g.ntaps;
+                    }
+                g.A2 = fcond;
+                g.lda2 = MP;
+                g.Cin2 = MP;
+                g.w2_slab0 = 9 * C / PK_GEMM_BK;
+                g.wslabs_total = (9 * C + MP) / PK_GEMM_BK;
+                g.Wp = h->W(L.w1);
+                g.Wh = h->arena16.as<uint16_t>() + L.w1h;
+                g.math = h->math;
+                g.bias = h->W(L.b1);
+                g.rowvalid = putt_flat;
+                g.M = (int)nflat;
+                g.N = 2 * C;
+                g.epi = PK_EPI_GATE;
+                g.C = zbuf;
+                g.ldc = C;
+                PK_TRY(pk_gemm_launch(ctx, "wf_gemm_conv_gate", g));
+                pk_gemm_args o;
+                o.A = zbuf;
+                o.lda = C;
+                o.Cin = C;
+                o.taps = 1;
+                o.pad = 0;
+                o.Wp = h->W(L.w2);
+                o.Wh = h->arena16.as<uint16_t>() + L.w2h;
+                o.math = h->math;
+                o.bias = h->W(L.b2);
+                o.res = in;
+                o.ldr = C;
+                o.C = out;
+                o.ldc = C;
+                o.nsplit = C;
+                o.C2 = skip;
+                o.ldc2 = C;
+                o.acc2 = l > 0;
+                o.rowvalid = putt_flat;
+                o.M = (int)nflat;
+                o.N = 2 * C;
+                PK_TRY(pk_gemm_launch(ctx, "wf_gemm_out_proj", o));
+            }
+            PK_LAUNCH(ctx, "wf_params_rows", k_wf_params_rows, dim3(pk_div_up(nflat, 4)), dim3(256), 0, skip, C, h->W(F.w_out), prm, nflat);
+        }
+        // z' = shuffle(transform(x)) and this flow's share of the log-determinant
+        WfRowMap dm;
+        memset(&dm, 0, sizeof(dm));
+        for (int r = 0; r < G; ++r) dm.row[r] = inv[r];
+        PK_LAUNCH(ctx, "wf_affine_rows", k_wf_affine_rows, dim3(pk_div_up(npos, 256), G), dim3(256), 0, cur, nxt, pstride, prm,
+                  (long)npos_alloc, b_logs, b_b, putt_flat, npos, dm);
+        PK_LAUNCH(ctx, "wf_logs_partial", k_wf_logs_partial, dim3(max_nch, R, B), dim3(256), 0, prm, (long)npos_alloc, b_logs,
+                  d_tab + o_woff, d_tab + o_wlen, d_tab + o_nch, d_tab + o_poff, part);
+        PK_LAUNCH(ctx, "wf_logdet_acc", k_wf_logdet_acc, dim3(B), dim3(64), 0, part, d_tab + o_nch, d_tab + o_poff, R, d_logdet, fl == 0 ? 1 : 0);
+        std::vector<int> cnew(G);
+        for (int i = 0; i < G; ++i) cnew[i] = cidx[perm[i]];   // cumulative shuffle of the condition (:665)
+        cidx = cnew;
+        std::swap(cur, nxt);
+    }
+    PK_LAUNCH(ctx, "wf_unfold", k_wf_unfold, dim3(pk_div_up(npos, 256)), dim3(256), 0, cur, putt_flat, d_tab + o_pw, d_tab + o_ooff, G,
+              npos, pstride, d_z);
+    if (flags & PK_HOST_IO) {
+        PK_HIP(hipMemcpyAsync(z, d_z, (size_t)sumO * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipMemcpyAsync(logdet, d_logdet, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PK_OK;
+}
+
 extern "C" void pk_wf_destroy(pk_wf* h) {
     if (!h) return;
     pk_device_guard _dg(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
     pk_dbuf* bufs[] = {&h->arena, &h->arena16, &h->ws_tab, &h->ws_mel, &h->ws_z, &h->ws_wav, &h->ws_u[0], &h->ws_u[1],
                        &h->ws_cond, &h->ws_cur, &h->ws_nxt, &h->ws_hist, &h->ws_zbuf, &h->ws_skip,
-                       &h->ws_hamax, &h->ws_camax, &h->ws_trace, &h->ws_bar, &h->ws_desc, &h->ws_replay};
+                       &h->ws_hamax, &h->ws_camax, &h->ws_trace, &h->ws_bar, &h->ws_desc, &h->ws_replay,
+                       &h->ws_fa, &h->ws_fb, &h->ws_fam, &h->ws_fcond, &h->ws_fcam, &h->ws_fprm, &h->ws_fpart, &h->ws_flogdet, &h->ws_fz,
+                       &h->ws_fskip};
     for (auto* b : bufs) b->release();
     delete h;
 }

@@ -1022,6 +1022,77 @@ __global__ __launch_bounds__(256) void k_wf_step_p(const float* __restrict__ prm
     }
 }
 
+// ---- the forward direction (ConditionalWaveFlow.forward, waveflow.hip pk_wf_forward): every row of the folded audio is known, so
+// the rows of a flow lie one behind the other on ONE position axis ("flat" rows: row r at positions [r * npos, (r + 1) * npos)) and a
+// layer of a flow is one launch of k_wf_layer_p over all of them.  The two kernels below write such rows.
+//
+// The condition rows of a flow in the order that flow sees them: dst row r (planes) = src row map[r] (fp32 [pos / 32][96][32], as
+// the upsampler wrote them) -- the cumulative row shuffle between flows (WaveFlow.forward :664-665) as an index map.
+__global__ __launch_bounds__(64) void k_wf_cond_planes_rows(const float* __restrict__ src, long src_row_stride, float* __restrict__ dst,
+                                                           long dst_row_stride, unsigned* __restrict__ amax, long amax_row_stride,
+                                                           WflRowMap map, int one_ch) {
+    const float* blk = src + (long)map.row[blockIdx.y] * src_row_stride + (long)blockIdx.x * (WFL_MP * WFL_BLK);
+    const int lane = threadIdx.x, j = lane & 31, hh = lane >> 5;
+    float v[WFL_KS_COND][8];
+    float m = 0.f;
+#pragma unroll
+    for (int kq = 0; kq < WFL_KS_COND; ++kq)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int ch = wfl_chan(kq, hh, e);
+            v[kq][e] = ch == one_ch ? 1.f : blk[ch * WFL_BLK + j];   // the constant channel that carries the layers' biases
+            m = fmaxf(m, fabsf(v[kq][e]));
+        }
+    m = wave_max64(m);
+    const float s = pow2f(blk_scale_exp(__float_as_uint(m)));
+    char* out = reinterpret_cast<char*>(dst + (long)blockIdx.y * dst_row_stride + (long)blockIdx.x * (WFL_MP * WFL_BLK)) + j * 32 + hh * 1024;
+#pragma unroll
+    for (int kq = 0; kq < WFL_KS_COND; ++kq) {
+        f16x8 oh, ol;
+        store_pair8(v[kq], s, oh, ol);
+        st_h8(out + kq * 2048, oh);
+        st_h8(out + kq * 2048 + 16, ol);
+    }
+    if (lane == 0) amax[(long)blockIdx.y * amax_row_stride + blockIdx.x] = __float_as_uint(m);
+}
+
+// input_proj (Flow._predict_parameters :453) of the rows 0 .. rows-1 of x at once: h0[row] = w_in x[row] + b_in as planes with
+// block maxima; gap positions are zeros.  One wave per (row, 32 positions), as k_wf_step_p.
+template <int CT>
+__global__ __launch_bounds__(256) void k_wf_inproj_rows_p(const float* __restrict__ x, long x_row_stride, const float* __restrict__ w_in,
+                                                          const float* __restrict__ b_in, float* __restrict__ h0, long h0_row_stride,
+                                                          unsigned* __restrict__ h0_amax, long amax_row_stride,
+                                                          const int* __restrict__ pos_utt, int npos_alloc) {
+    constexpr int C = 32 * CT, KS = C / 16;
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), row = blockIdx.y;
+    if (tile * WAVE_T >= npos_alloc) return;
+    const int lane = threadIdx.x & 63, j = lane & 31, hh = lane >> 5;
+    const int p = tile * WAVE_T + j;
+    const bool valid = pos_utt[p] >= 0;
+    const float xn = valid ? x[(long)row * x_row_stride + p] : 0.f;
+    float v[KS][8];
+    float am = 0.f;
+#pragma unroll
+    for (int kq = 0; kq < KS; ++kq)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = wfl_chan(kq, hh, e);
+            v[kq][e] = valid ? fmaf(w_in[c], xn, b_in[c]) : 0.f;
+            am = fmaxf(am, fabsf(v[kq][e]));
+        }
+    am = wave_max64(am);
+    const float s = pow2f(blk_scale_exp(__float_as_uint(am)));
+    char* dst = reinterpret_cast<char*>(h0 + (long)row * h0_row_stride) + (long)tile * (C * 128) + j * 32 + hh * 1024;
+#pragma unroll
+    for (int kq = 0; kq < KS; ++kq) {
+        f16x8 oh, ol;
+        store_pair8(v[kq], s, oh, ol);
+        st_h8(dst + kq * 2048, oh);
+        st_h8(dst + kq * 2048 + 16, ol);
+    }
+    if (lane == 0) h0_amax[(long)row * amax_row_stride + tile] = __float_as_uint(am);
+}
+
 inline uint16_t f32_to_f16_rne(float f) {
     uint32_t x;
     memcpy(&x, &f, 4);
@@ -1271,5 +1342,27 @@ int wfl_step_launch(pk_ctx* ctx, int C, const float* prm, float b_logs, float b_
     else
         PK_LAUNCH(ctx, "wf_step", k_wf_step_p<4>, grid, dim3(256), 0, prm, b_logs, b_b, z_row, x_row, w_in, b_in, h0_next,
                   h0_amax, pos_utt, npos_alloc, first);
+    return PK_OK;
+}
+
+int wfl_cond_planes_rows_launch(pk_ctx* ctx, const float* src, long src_row_stride, float* dst, long dst_row_stride, unsigned* amax,
+                                long amax_row_stride, const WflRowMap& map, int rows, int nblk, int n_mels) {
+    if (n_mels >= WFL_MP) PK_FAIL(PK_EUNSUPPORTED, "the fused WaveFlow layer kernel needs a free condition channel (n_mels < %d)", WFL_MP);
+    if (rows < 1 || rows > WFL_MAX_ROWS) PK_FAIL(PK_EINVAL, "wfl_cond_planes_rows_launch: %d rows", rows);
+    PK_LAUNCH(ctx, "wf_cond_planes_rows", k_wf_cond_planes_rows, dim3(nblk, rows), dim3(64), 0, src, src_row_stride, dst, dst_row_stride,
+              amax, amax_row_stride, map, n_mels);
+    return PK_OK;
+}
+
+int wfl_inproj_rows_launch(pk_ctx* ctx, int C, const float* x, long x_row_stride, const float* w_in, const float* b_in, float* h0,
+                           long h0_row_stride, unsigned* h0_amax, long amax_row_stride, const int* pos_utt, int npos_alloc, int rows) {
+    if (!wfl_supports(C) || npos_alloc % WAVE_T != 0 || rows < 1) PK_FAIL(PK_EINVAL, "wfl_inproj_rows_launch: bad shape (C %d, npos %d, rows %d)", C, npos_alloc, rows);
+    const dim3 grid(pk_div_up(npos_alloc / WAVE_T, 4), rows);
+    if (C == 64)
+        PK_LAUNCH(ctx, "wf_inproj_rows", k_wf_inproj_rows_p<2>, grid, dim3(256), 0, x, x_row_stride, w_in, b_in, h0, h0_row_stride, h0_amax,
+                  amax_row_stride, pos_utt, npos_alloc);
+    else
+        PK_LAUNCH(ctx, "wf_inproj_rows", k_wf_inproj_rows_p<4>, grid, dim3(256), 0, x, x_row_stride, w_in, b_in, h0, h0_row_stride, h0_amax,
+                  amax_row_stride, pos_utt, npos_alloc);
     return PK_OK;
 }

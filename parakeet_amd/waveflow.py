@@ -1,9 +1,12 @@
 """WaveFlow vocoder behind the reference's Python API.
 
-Mirrors parakeet/models/waveflow.py ``ConditionalWaveFlow`` (constructor :741-757, ``infer``
-:785-805, ``predict`` :808-825); all arithmetic runs in libpk_synth.so (csrc/waveflow.hip).
-Extension: ``infer`` takes an optional ``z=`` (the reference draws ``paddle.randn`` inside).
-Synthesis only -- ``forward`` / ``WaveFlowLoss`` are training-time and out of scope.
+Mirrors parakeet/models/waveflow.py ``ConditionalWaveFlow`` (constructor :741-757, ``forward`` :759-782, ``infer``
+:785-805, ``predict`` :808-825) and ``WaveFlowLoss`` (:855-891); all arithmetic of the model runs in libpk_synth.so
+(csrc/waveflow.hip).  Both directions: ``infer`` samples (autoregressive over the rows of the folded signal), ``forward`` is
+density estimation -- audio to the latent ``z`` and the log-determinant, hence the exact log-likelihood of a recording under the
+vocoder -- and runs every row of a flow at once.  No backward pass: the engine does not train.
+Extensions: ``infer`` takes an optional ``z=`` (the reference draws ``paddle.randn`` inside); ``forward_batch`` /
+``log_likelihood`` take ragged lists and answer per utterance.
 """
 import ctypes as C
 
@@ -13,7 +16,28 @@ import torch
 from . import _capi, amp
 from .runtime import Context, dptr, set_params, wrap
 
+__all__ = ["ConditionalWaveFlow", "WaveFlowLoss"]
+
 _MATH = {"f32": 0, "f16x3": 1, "f16": 2}
+
+
+class WaveFlowLoss:
+    """waveflow.py:855-891: the negative log-likelihood per sample of ``z`` under N(0, sigma^2) with the flow's
+    log-determinant -- ``sum(z^2) / (2 sigma^2) - log_det_jacobian`` over ``prod(z.shape)`` plus ``const``."""
+
+    def __init__(self, sigma=1.0):
+        self.sigma = sigma
+        self.const = 0.5 * np.log(2 * np.pi) + np.log(self.sigma)
+
+    def forward(self, z, log_det_jacobian):
+        z = z.as_subclass(torch.Tensor) if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
+        ldj = log_det_jacobian
+        ldj = ldj.as_subclass(torch.Tensor) if isinstance(ldj, torch.Tensor) else torch.as_tensor(np.asarray(ldj))
+        loss = torch.sum(z * z) / (2 * self.sigma * self.sigma) - ldj.to(z.device)
+        loss = loss / int(np.prod(z.shape))
+        return wrap(loss + self.const)
+
+    __call__ = forward
 
 
 class ConditionalWaveFlow:
@@ -111,6 +135,72 @@ class ConditionalWaveFlow:
             outs.append(wrap(wav[o:o + n]))
             o += n
         return outs
+
+    def forward_length(self, t_mel, n_audio):
+        """Length of ``z`` for ``n_audio`` samples with ``t_mel`` frames (the audio cut to a multiple of n_group, :617-625)."""
+        n = C.c_int32()
+        _capi.check(self._ctx.lib.pk_wf_forward_length(self._h, int(t_mel), int(n_audio), C.byref(n)))
+        return n.value
+
+    def forward_batch(self, audios, mels):
+        """Density estimation of a ragged batch.  audios: list of (T_b,) arrays, mels: list of (C_mel, T_mel_b) arrays with
+        ``n_group <= T_b <= T_mel_b * hop`` (the untrimmed upsampled mel must cover the audio, waveflow.py:618, 780).
+        Returns a list of ``(z_b, logdet_b)``: z_b (T_b // n_group * n_group,) fp32 device tensor, logdet_b a 0-d fp64 device
+        tensor (the sum of logs of utterance b).  An utterance's results do not depend on the rest of the batch."""
+        ctx = Context.get(self._ctx.device)
+        if not self._finalized:
+            _capi.check(ctx.lib.pk_wf_finalize(self._h))
+            self._finalized = True
+        assert len(audios) == len(mels) and len(mels) > 0
+        frames = np.array([int(m.shape[-1]) for m in mels], dtype=np.int32)
+        auds = [ctx.to_device(a).reshape(-1) for a in audios]
+        alen = np.array([int(a.numel()) for a in auds], dtype=np.int32)
+        zlen = [self.forward_length(int(f), int(n)) for f, n in zip(frames, alen)]   # raises ValueError on a bad length
+        mel = torch.cat([ctx.to_device(m).reshape(self.n_mels, -1).transpose(0, 1) for m in mels], 0).contiguous()
+        audio = torch.cat(auds).contiguous()
+        z = ctx.empty((sum(zlen),))
+        logdet = ctx.empty((len(mels),), dtype=torch.float64)
+        cast = amp.enabled() and self._math != "f16"   # as infer_batch: fp16 operands inside amp.auto_cast
+        if cast:
+            _capi.check(ctx.lib.pk_wf_set_math(self._h, _MATH["f16"]))
+        try:
+            i32p = C.POINTER(C.c_int32)
+            _capi.check(ctx.lib.pk_wf_forward(self._h, dptr(mel), frames.ctypes.data_as(i32p), dptr(audio), alen.ctypes.data_as(i32p),
+                                              len(mels), dptr(z), dptr(logdet), 0))
+        finally:
+            if cast:
+                _capi.check(ctx.lib.pk_wf_set_math(self._h, _MATH[self._math]))
+        outs, o = [], 0
+        for b, n in enumerate(zlen):
+            outs.append((wrap(z[o:o + n]), wrap(logdet[b])))
+            o += n
+        return outs
+
+    def forward(self, audio, mel):
+        """audio (B, T), mel (B, C_mel, T_mel) -> (z (B, T // n_group * n_group), log_det_jacobian (1,) fp32: the sum over the
+        batch); waveflow.py:759-782."""
+        ctx = Context.get(self._ctx.device)
+        audio, mel = ctx.to_device(audio), ctx.to_device(mel)
+        if not self._finalized:     # (before the length check: a call before the weights are set is a state error first)
+            _capi.check(ctx.lib.pk_wf_finalize(self._h))
+            self._finalized = True
+        outs = self.forward_batch([audio[b] for b in range(mel.shape[0])], [mel[b] for b in range(mel.shape[0])])
+        z = torch.stack([o.as_subclass(torch.Tensor) for o, _ in outs], 0)
+        ldj = torch.stack([l.as_subclass(torch.Tensor) for _, l in outs]).sum().to(torch.float32).reshape(1)
+        return wrap(z), wrap(ldj)
+
+    __call__ = forward
+
+    def log_likelihood(self, audios, mels, sigma=1.0):
+        """Mean log-likelihood in nats per sample of each utterance (ragged lists as forward_batch): minus WaveFlowLoss(sigma) of
+        that utterance alone.  Returns a list of floats."""
+        const = 0.5 * np.log(2 * np.pi) + np.log(sigma)
+        out = []
+        for z, ld in self.forward_batch(audios, mels):
+            zz = z.as_subclass(torch.Tensor).double()
+            nll = (float(torch.sum(zz * zz)) / (2 * sigma * sigma) - float(ld)) / zz.numel() + const
+            out.append(-nll)
+        return out
 
     def infer(self, mel, z=None):
         """(B, C_mel, T_mel) -> (B, T); waveflow.py:785-805."""

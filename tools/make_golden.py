@@ -186,3 +186,5 @@ if __name__ == "__main__":
     golden_pwg()
     from make_golden_waveflow import golden_waveflow
     golden_waveflow(OUT)
+    from make_golden_waveflow_forward import golden_waveflow_forward
+    golden_waveflow_forward(OUT)

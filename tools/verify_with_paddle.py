@@ -47,7 +47,7 @@ sys.path.insert(0, HERE)
 import ref_import  # noqa: E402
 
 ROOT = ref_import.ROOT
-GENERATORS = ["make_golden.py", "make_golden_speedyspeech.py", "make_golden_ar.py", "make_golden_pwg_sizes.py", "make_golden_tts_teacher.py"]
+GENERATORS = ["make_golden.py", "make_golden_speedyspeech.py", "make_golden_ar.py", "make_golden_pwg_sizes.py", "make_golden_tts_teacher.py", "make_golden_waveflow_forward.py"]
 
 # CMU phones with stress marks as g2p_en emits them + the recipe's extra symbols (examples/fastspeech2/ljspeech: the
 # released phone_id_map.txt is data-derived, parakeet/datasets/preprocess_utils.py:92-103: <pad>, <unk>, phones, punctuation, <eos>)
