@@ -659,6 +659,53 @@ void pk_mel_destroy(pk_mel* h);
 int pk_op_average_by_duration(pk_ctx* ctx, const float* x, int64_t frames, int32_t C, const int64_t* durations,
                               int32_t T, float* out);
 
+/* ------------------------------------------------ inverse STFT / Griffin-Lim */
+/* parakeet/audio/audio.py AudioProcessor.istft (:86-93) = librosa.istft: every frame is irfft(D[:, f], n_fft) * window
+ * (the imaginary parts of DC and Nyquist are ignored, as numpy.fft.irfft does), frames are overlap-added at stride
+ * hop_length, every sample is divided by the overlap-added window^2 where that envelope exceeds FLT_MIN and left
+ * undivided elsewhere, and with center n_fft/2 samples are cut from both ends.
+ * Limits as for the STFT: n_fft a multiple of 16 (and <= 16384), hop_length a multiple of 4, else PK_EUNSUPPORTED.
+ * The overlap-add is a gather in ascending frame order without atomics and shares nothing between utterances: the
+ * samples of an utterance are bit-identical in any batch and at any position in it. */
+typedef struct pk_istft pk_istft;
+typedef struct {
+    int32_t n_fft;
+    int32_t hop_length;
+    int32_t center;       /* 1: the spectra come from a centred STFT; n_fft/2 samples are trimmed from both ends */
+} pk_istft_cfg;
+/* window: n_fft floats, centre-padded to n_fft as for pk_mel_create. */
+int pk_istft_create(pk_ctx* ctx, const pk_istft_cfg* cfg, const float* window, pk_istft** out);
+/* samples returned for `frames` >= 1 frames: hop * (frames - 1) with center, else n_fft + hop * (frames - 1). */
+int pk_istft_num_samples(pk_istft* h, int32_t frames, int32_t* n);
+/* spec: (sum(frames), 2*n_bin) real | imag, packed by utterance and time-major -- what pk_mel_run(what = 0) writes;
+ * frames (B) host, each >= 1 (else PK_EINVAL); wav_out packed by utterance, pk_istft_num_samples floats each.
+ * flags: PK_HOST_IO if spec / wav_out are host pointers (then synchronous). */
+int pk_istft_run(pk_istft* h, const float* spec, const int32_t* frames, int32_t B, float* wav_out, int32_t flags);
+/* Fast Griffin-Lim (librosa.griffinlim; Perraudin, Balazs, Sondergaard 2013): phases for a magnitude spectrogram.
+ *   angles = initial phases; rebuilt = 0
+ *   n_iter times: previous = rebuilt; rebuilt = STFT(ISTFT(mag * angles));
+ *                 angles = rebuilt - momentum / (1 + momentum) * previous; angles /= |angles| + 1e-16
+ *   wav_out = ISTFT(mag * angles)
+ * momentum = 0 is the classic algorithm; n_iter = 0 is pk_istft_run of mag * angles, bit for bit.  All iterations are
+ * enqueued on the context's stream without a host synchronisation in between.
+ *   stft    a pk_mel handle of the same context with the same n_fft, hop_length, center (and window); its packed basis
+ *           runs the forward transform.  A mismatch -> PK_EINVAL.
+ *   mag     (sum(frames), n_bin) packed like spec;  frames (B) host.  With center and n_iter > 0 an utterance needs
+ *           hop * (frames - 1) > n_fft / 2 (the forward STFT reflect-pads it), else PK_EINVAL.
+ *   angles  (sum(frames), 2*n_bin) cos | sin, or NULL: exp(2 pi i u) with u = word * 2^-32, word (bin & 3) of the
+ *           Philox4x32-10 block with counter (frame index inside its utterance, bin >> 2, 0, 0x474C5048 "GLPH") and
+ *           key seeds[b] -- a seed reproduces an utterance exactly in any batch (the contract of the dropout stream).
+ *   seeds   (B) host, NULL = all 0; unused when angles are given
+ *   n_iter >= 0, 0 <= momentum < 1, else PK_EINVAL.
+ * flags: PK_HOST_IO if mag / angles / wav_out are host pointers (then synchronous). */
+int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int32_t* frames, int32_t B, int32_t n_iter,
+              float momentum, const uint64_t* seeds, const float* angles, float* wav_out, int32_t flags);
+/* Test taps of the last pk_gl_run, copied to HOST as (sum(frames), 2*n_bin) re | im, n = that many floats (else PK_ESHAPE):
+ * 0 = the spectrum the last iteration's forward STFT rebuilt (PK_ESTATE after n_iter = 0), 1 = the last iterate
+ * mag * angles, the spectrum the returned waveform is the ISTFT of. */
+int pk_gl_debug_read(pk_istft* h, int32_t what, float* out, int64_t n);
+void pk_istft_destroy(pk_istft* h);
+
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).
  * Replaces the paddle.randn calls of PWGGenerator.inference (parallel_wavegan.py:515-516) and

@@ -95,6 +95,10 @@ class SpkCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_mels", "num_layers", "hidden_size", "output_size")]
 
 
+class IstftCfg(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32)]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -202,6 +206,12 @@ def _declare(lib):
         "pk_mel_num_frames": (C.c_int, [vp, i32, i32p]),
         "pk_mel_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32, i32]),
         "pk_mel_destroy": (None, [vp]),
+        "pk_istft_create": (C.c_int, [vp, C.POINTER(IstftCfg), f32p, C.POINTER(vp)]),
+        "pk_istft_num_samples": (C.c_int, [vp, i32, i32p]),
+        "pk_istft_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_gl_run": (C.c_int, [vp, vp, f32p, i32p, i32, i32, C.c_float, C.POINTER(C.c_uint64), f32p, f32p, i32]),
+        "pk_gl_debug_read": (C.c_int, [vp, i32, f32p, i64]),
+        "pk_istft_destroy": (None, [vp]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),

@@ -6,6 +6,10 @@ the arithmetic (reflect padding, DFT-as-GEMM, magnitude, mel GEMM, log) runs in 
 (csrc/mel.hip).  The window and the mel filterbank are host-side constants handed to the engine;
 ``mel_filterbank`` follows the algorithm of librosa.filters.mel (Slaney scale and normalisation),
 which the reference calls at audio.py:221 / get_feats.py:49-55.
+
+The way back -- ``ISTFT``, ``AudioProcessor.stft`` / ``istft`` / ``griffin_lim`` / ``mel_to_linear`` and the weight-free
+``GriffinLim`` vocoder -- follows parakeet/audio/audio.py:75-93 (librosa's ``istft``) and ``librosa.griffinlim``; it runs in
+csrc/istft.hip.
 """
 import ctypes as C
 import math
@@ -127,6 +131,106 @@ class STFT:
 
     def magnitude(self, x):
         return wrap(self._batch(x, self._mag, 1))
+
+
+class _InvEngine:
+    """A pk_istft handle: packed (frames, 2*n_bin) re | im rows -> samples, and the Griffin-Lim loop around it."""
+
+    def __init__(self, n_fft, hop_length, win_length, window, center, device=None):
+        self.ctx = Context.get(device)
+        cfg = _capi.IstftCfg(n_fft, hop_length, 1 if center else 0)
+        self.n_fft, self.n_bin = n_fft, 1 + n_fft // 2
+        win = _window(window, win_length or n_fft, n_fft)
+        h = C.c_void_p()
+        _capi.check(self.ctx.lib.pk_istft_create(self.ctx.handle, C.byref(cfg), _capi.fptr(win), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.ctx.lib.pk_istft_destroy(h)
+            except Exception:
+                pass
+
+    def samples(self, frames):
+        n = C.c_int32()
+        _capi.check(self.ctx.lib.pk_istft_num_samples(self.h, int(frames), C.byref(n)))
+        return n.value
+
+    def _rows(self, mats, cols, what):
+        ctx = Context.get(self.ctx.device)
+        mats = [ctx.to_device(m) for m in mats]
+        for m in mats:
+            if m.dim() != 2 or m.shape[1] != cols:
+                raise AssertionError(f"{what}: expected (frames, {cols}) rows, got {tuple(m.shape)}")
+        return ctx, torch.cat(mats), np.array([m.shape[0] for m in mats], dtype=np.int32)
+
+    def _out(self, ctx, frames):
+        # at least one float: an empty tensor has no address to hand to the engine (which refuses frames < 1 itself)
+        return ctx.empty((max(1, sum(self.samples(f) for f in frames if f >= 1)),))
+
+    def _split(self, out, frames):
+        res, o = [], 0
+        for f in frames:
+            n = self.samples(f)
+            res.append(out[o:o + n])
+            o += n
+        return res
+
+    def run(self, specs):
+        """specs: list of (frames_b, 2*n_bin) re | im -> list of (T_b,) device tensors."""
+        ctx, x, frames = self._rows(specs, 2 * self.n_bin, "ISTFT")
+        out = self._out(ctx, frames)
+        _capi.check(ctx.lib.pk_istft_run(self.h, dptr(x), frames.ctypes.data_as(C.POINTER(C.c_int32)), len(frames),
+                                         dptr(out), 0))
+        return self._split(out, frames)
+
+    def griffin_lim(self, stft_engine, mags, n_iter=32, momentum=0.99, seeds=None, angles=None):
+        """mags: list of (frames_b, n_bin); angles: None or a list of (frames_b, 2*n_bin) cos | sin; seeds: None or one
+        integer per utterance -> list of (T_b,) device tensors."""
+        ctx, s, frames = self._rows(mags, self.n_bin, "Griffin-Lim magnitudes")
+        a = None
+        if angles is not None:
+            _, a, fa = self._rows(angles, 2 * self.n_bin, "Griffin-Lim angles")
+            if not np.array_equal(fa, frames):
+                raise AssertionError("Griffin-Lim: angles and magnitudes differ in their frame counts")
+        sd = None
+        if seeds is not None:
+            sd = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64)
+            if sd.size != len(frames):
+                raise AssertionError("Griffin-Lim: one seed per utterance is needed")
+        out = self._out(ctx, frames)
+        _capi.check(ctx.lib.pk_gl_run(self.h, stft_engine.h, dptr(s), frames.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      len(frames), int(n_iter), float(momentum),
+                                      None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      None if a is None else dptr(a), dptr(out), 0))
+        return self._split(out, frames)
+
+
+class ISTFT:
+    """real, imag (B, n_bin, frames) -> (B, T): the inverse of ``STFT`` (librosa's ``istft``, audio.py:86-93)."""
+
+    def __init__(self, n_fft, hop_length=None, win_length=None, window="hanning", center=True):
+        win_length = win_length or n_fft
+        hop_length = hop_length or int(win_length // 4)
+        self.n_fft, self.hop_length, self.n_bin, self.center = n_fft, hop_length, 1 + n_fft // 2, center
+        self._eng = _InvEngine(n_fft, hop_length, win_length, window, center)
+
+    def forward(self, real, imag):
+        ctx = Context.get()
+        real, imag = ctx.to_device(real), ctx.to_device(imag)
+        if real.dim() != 3 or real.shape != imag.shape or real.shape[1] != self.n_bin:
+            raise AssertionError(f"ISTFT: expected two (B, {self.n_bin}, frames) tensors, got {tuple(real.shape)} and "
+                                 f"{tuple(imag.shape)}")
+        rows = torch.cat([real, imag], 1).transpose(1, 2).contiguous()          # (B, frames, re | im)
+        return wrap(torch.stack(self._eng.run([rows[b] for b in range(rows.shape[0])]), 0))
+
+    __call__ = forward
+
+    def inverse_batch(self, specs):
+        """Ragged: a list of (frames_b, 2*n_bin) re | im rows (``pk_mel_run`` what = 0) -> a list of (T_b,)."""
+        return [wrap(o) for o in self._eng.run(list(specs))]
 
 
 class MelScale:
@@ -334,6 +438,7 @@ class AudioProcessor:
         self.inv_mel_filter = np.linalg.pinv(self.mel_filter)
         self._spec = _Engine(n_fft, hop_length, win_length, window, center, False, None, 0)
         self._mel = _Engine(n_fft, hop_length, win_length, window, center, False, self.mel_filter, 0)
+        self._inv = None
 
     def read_wav(self, filename):
         import wave
@@ -358,3 +463,91 @@ class AudioProcessor:
 
     def mel_spectrogram(self, wav):
         return self._mel.run([np.asarray(wav, dtype=np.float32)], 2)[0].cpu().numpy().T
+
+    def stft(self, wav):
+        """complex64 (n_bin, frames), audio.py:75-84."""
+        o = self._spec.run([np.asarray(wav, dtype=np.float32)], 0)[0].cpu().numpy()
+        nb = self._spec.n_bin
+        return (o[:, :nb] + 1j * o[:, nb:]).T.astype(np.complex64)
+
+    def _inverse(self):
+        if self._inv is None:
+            self._inv = _InvEngine(self.n_fft, self.hop_length, self.win_length, self.window, self.center)
+        return self._inv
+
+    @staticmethod
+    def _reim_rows(D):
+        D = np.asarray(D)
+        return np.ascontiguousarray(np.concatenate([D.real.T, D.imag.T], axis=1), dtype=np.float32)
+
+    def istft(self, D):
+        """complex (n_bin, frames) -> float32 (T,), audio.py:86-93."""
+        return self._inverse().run([self._reim_rows(D)])[0].cpu().numpy()
+
+    def griffin_lim_batch(self, specs, n_iter=32, momentum=0.99, seeds=None, angles=None):
+        """Ragged ``griffin_lim``: a list of (n_bin, frames_b) magnitudes (and complex initial phases) -> list of (T_b,)."""
+        ctx = Context.get()
+        mags = [ctx.to_device(S).transpose(0, 1) for S in specs]
+        ang = None if angles is None else [self._reim_rows(a) for a in angles]
+        out = self._inverse().griffin_lim(self._spec, mags, n_iter, momentum, seeds, ang)
+        return [o.cpu().numpy() for o in out]
+
+    def griffin_lim(self, S, n_iter=32, momentum=0.99, seed=0, angles=None):
+        """``librosa.griffinlim`` on the engine: S (n_bin, frames) magnitudes as ``spectrogram`` returns them -> float32
+        (T,).  ``angles``: complex (n_bin, frames) initial phases of unit modulus; None draws them from ``seed``."""
+        return self.griffin_lim_batch([S], n_iter, momentum, [seed], None if angles is None else [angles])[0]
+
+    def _mel_to_linear_rows(self, x):
+        """(rows, n_mels) device -> (rows, n_bin) device: one engine GEMM over frames and the floor."""
+        ctx = Context.get()
+        if x.dim() != 2 or x.shape[1] != self.n_mels:
+            raise AssertionError(f"mel_to_linear: expected {self.n_mels} mel bins, got {tuple(x.shape)}")
+        nb = self.inv_mel_filter.shape[0]
+        y = ctx.empty((x.shape[0], nb))
+        wkn = np.ascontiguousarray(self.inv_mel_filter.T, dtype=np.float32)        # [n_mels][n_bin]
+        _capi.check(ctx.lib.pk_op_matmul(ctx.handle, dptr(x), x.shape[0], self.n_mels, nb, _capi.fptr(wkn), None, dptr(y)))
+        return torch.clamp_min(y, 1e-10)
+
+    def mel_to_linear(self, mel):
+        """``maximum(1e-10, inv_mel_filter @ mel)``: (n_mels, frames) -> (n_bin, frames) numpy."""
+        x = Context.get().to_device(mel)
+        if x.dim() != 2:
+            raise AssertionError(f"mel_to_linear: expected (n_mels, frames), got {tuple(x.shape)}")
+        return self._mel_to_linear_rows(x.transpose(0, 1).contiguous()).cpu().numpy().T
+
+
+class GriffinLim:
+    """A weight-free vocoder: mel -> ``spec_normalizer.inverse`` -> ``mel_to_linear`` -> ``** power`` -> Griffin-Lim.
+    ``spec_normalizer`` is e.g. ``LogMagnitude()`` for the Tacotron2 / TransformerTTS / WaveFlow feature domain (its inverse
+    is a plain exp); None takes the mel as linear magnitudes."""
+
+    def __init__(self, audio_processor, spec_normalizer=None, n_iter=32, momentum=0.99, power=1.0):
+        self.audio_processor, self.spec_normalizer = audio_processor, spec_normalizer
+        self.n_iter, self.momentum, self.power = n_iter, momentum, power
+
+    def infer_batch(self, mels, seeds=None):
+        """A list of (n_mels, frames_b) -> a list of float32 (T_b,); ``seeds``: one integer per utterance (default 0)."""
+        ap, ctx = self.audio_processor, Context.get()
+        mels = [np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float32) for m in mels]
+        for m in mels:
+            if m.ndim != 2 or m.shape[0] != ap.n_mels:
+                raise AssertionError(f"GriffinLim: expected ({ap.n_mels}, frames) mels, got {m.shape}")
+        if self.spec_normalizer is not None:
+            mels = [np.asarray(self.spec_normalizer.inverse(m), dtype=np.float32) for m in mels]
+        lin = ap._mel_to_linear_rows(ctx.to_device(np.concatenate([m.T for m in mels], axis=0)))   # one GEMM for the batch
+        if self.power != 1.0:
+            lin = torch.pow(lin, float(self.power))
+        specs, o = [], 0
+        for m in mels:
+            specs.append(lin[o:o + m.shape[1]].transpose(0, 1))
+            o += m.shape[1]
+        return ap.griffin_lim_batch(specs, self.n_iter, self.momentum, seeds)
+
+    def infer(self, mel, seed=0):
+        """(n_mels, frames) -> (T,), or (B, n_mels, frames) -> (B, T)."""
+        mel = np.asarray(mel.cpu() if isinstance(mel, torch.Tensor) else mel, dtype=np.float32)
+        if mel.ndim == 2:
+            return self.infer_batch([mel], [seed])[0]
+        return np.stack(self.infer_batch(list(mel), [seed] * mel.shape[0]))
+
+    __call__ = infer

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pk_gemm.h"
+#include "pk_mel.h"
 
 namespace {
 
@@ -143,6 +144,10 @@ extern "C" int pk_mel_create(pk_ctx* ctx, const pk_mel_cfg* cfg, const float* wi
     *out = h;
     return PK_OK;
 }
+
+const pk_mel_cfg* pk_mel_config(const pk_mel* h) { return &h->cfg; }
+pk_ctx* pk_mel_context(const pk_mel* h) { return h->ctx; }
+const float* pk_mel_dft_packed(const pk_mel* h) { return h->d_dft.as<float>(); }
 
 extern "C" int pk_mel_num_frames(pk_mel* h, int32_t n_samples, int32_t* frames) {
     if (!h || !frames) PK_FAIL(PK_EINVAL, "pk_mel_num_frames: NULL argument");
