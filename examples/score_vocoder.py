@@ -1,0 +1,66 @@
+"""Score vocoder output against the recordings with the multi-resolution STFT loss of the Parallel WaveGAN recipes: for every
+<utt_id>.wav in --gen-dir with a <utt_id>.wav in --ref-dir (16-bit PCM, same rate) print the utterance id, the samples
+scored, the spectral convergence loss and the log STFT magnitude loss (each the mean over the resolutions), then the corpus
+means of the two -- what the reference's evaluator reports as eval/spectral_convergence_loss and
+eval/log_stft_magnitude_loss when it scores one utterance per batch.  A pair of unequal length is trimmed to the shorter one,
+and the line says so.
+
+    python examples/score_vocoder.py --gen-dir generated --ref-dir recordings [--config conf/default.yaml]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from parakeet_amd.ge2e_audio import read_wav  # noqa: E402
+from parakeet_amd.stft_loss import MultiResolutionSTFTLoss  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--gen-dir", required=True, help="generated waveforms")
+    ap.add_argument("--ref-dir", required=True, help="recordings")
+    ap.add_argument("--config", default=None, help="Parallel WaveGAN yaml; its stft_loss_params are used (default: the "
+                                                   "reference's 1024/120/600, 2048/240/1200, 512/50/240, hann)")
+    ap.add_argument("--batch", type=int, default=16, help="pairs per call")
+    a = ap.parse_args()
+    params = {}
+    if a.config:
+        import yaml
+        with open(a.config) as f:
+            params = dict(yaml.safe_load(f).get("stft_loss_params") or {})
+    crit = MultiResolutionSTFTLoss(**params)
+    need = max(crit.fft_sizes) // 2 + 1
+    ids = sorted(f[:-4] for f in os.listdir(a.gen_dir) if f.endswith(".wav") and os.path.exists(os.path.join(a.ref_dir, f)))
+    if not ids:
+        raise SystemExit("no <utt_id>.wav present in both directories")
+    rows = []
+    for i in range(0, len(ids), a.batch):
+        xs, ys, kept, notes = [], [], [], []
+        for u in ids[i:i + a.batch]:
+            (x, sx), (y, sy) = read_wav(os.path.join(a.gen_dir, u + ".wav")), read_wav(os.path.join(a.ref_dir, u + ".wav"))
+            if sx != sy:
+                raise SystemExit(f"{u}: generated at {sx} Hz, recording at {sy} Hz")
+            n = min(len(x), len(y))
+            if n < need:
+                print(f"{u}\tskipped: {n} samples, the largest transform needs {need}", file=sys.stderr)
+                continue
+            notes.append("" if len(x) == len(y) else f"\ttrimmed from {len(x)} / {len(y)}")
+            xs.append(x[:n])
+            ys.append(y[:n])
+            kept.append(u)
+        if not kept:
+            continue
+        per = crit.per_utterance(xs, ys).mean(axis=1)            # (B, 2): mean over the resolutions
+        for u, x, (sc, mag), note in zip(kept, xs, per, notes):
+            print(f"{u}\t{len(x)}\t{sc:.6f}\t{mag:.6f}{note}")
+            rows.append((sc, mag))
+    if rows:
+        sc, mag = np.mean(rows, axis=0)
+        print(f"spectral_convergence_loss\t{sc:.6f}\nlog_stft_magnitude_loss\t{mag:.6f}\tover {len(rows)} utterances")
+
+
+if __name__ == "__main__":
+    main()

@@ -706,6 +706,41 @@ int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int32_t* frames
 int pk_gl_debug_read(pk_istft* h, int32_t what, float* out, int64_t n);
 void pk_istft_destroy(pk_istft* h);
 
+/* ------------------------------------------- multi-resolution STFT distance */
+/* parakeet/modules/stft_loss.py: what MultiResolutionSTFTLoss (:163-219) needs of two signals, reduced on the device.
+ * A handle holds R resolutions.  n_fft must be a multiple of 16 (else PK_EUNSUPPORTED); hop_length is ANY integer >= 1
+ * (a handle of its own: pk_mel_* and pk_istft_* keep their hop % 4 == 0 limit). */
+typedef struct pk_stftd pk_stftd;
+typedef struct {
+    int32_t n_fft;        /* 1024 */
+    int32_t hop_length;   /* 120 */
+    int32_t center;       /* 1: reflect-pad n_fft/2 on both sides */
+} pk_stftd_resolution;
+typedef struct {
+    int32_t n_res;        /* R */
+    float power_floor;    /* 1e-7: X = sqrt(max(re^2 + im^2, power_floor))  (stft_loss.py:66) */
+    float log_floor;      /* 1e-7: ln(max(X, log_floor))                    (:98, :117-118) */
+} pk_stftd_cfg;
+/* res: R entries; windows: the R windows one after the other, n_fft floats each, centre-padded as for pk_mel_create. */
+int pk_stftd_create(pk_ctx* ctx, const pk_stftd_cfg* cfg, const pk_stftd_resolution* res, const float* windows,
+                    pk_stftd** out);
+/* frames of resolution r = 1 + (n_samples + 2*pad - n_fft) / hop. */
+int pk_stftd_num_frames(pk_stftd* h, int32_t r, int32_t n_samples, int32_t* frames);
+/* x (predicted), y (ground truth): packed samples of B utterances with the same lens (B, host).
+ * sums_out (B, R, 3) float64, per utterance and resolution over its frames x n_bin entries:
+ *   [0] sum (Y - X)^2    [1] sum Y^2    [2] sum |ln max(Y, log_floor) - ln max(X, log_floor)|
+ * (terms in fp32, a frame's terms added in fp32, an utterance's frames in fp64).  No magnitude is stored.  An utterance's
+ * sums are bit-identical in any batch and at any position in it.
+ * PK_EINVAL: NULL pointer, B <= 0, an utterance with lens <= n_fft/2 of a centred resolution (reflect padding).
+ * flags: PK_HOST_IO if x / y / sums_out are host pointers (then synchronous). */
+int pk_stftd_run(pk_stftd* h, const float* x, const float* y, const int32_t* lens, int32_t B, double* sums_out,
+                 int32_t flags);
+/* The floored magnitude of resolution r: out packed (sum(frames), n_bin), by utterance and time-major.  Errors and flags
+ * as pk_stftd_run. */
+int pk_stftd_magnitude(pk_stftd* h, int32_t r, const float* wav, const int32_t* lens, int32_t B, float* out,
+                       int32_t flags);
+void pk_stftd_destroy(pk_stftd* h);
+
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).
  * Replaces the paddle.randn calls of PWGGenerator.inference (parallel_wavegan.py:515-516) and

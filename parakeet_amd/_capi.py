@@ -104,6 +104,14 @@ class MelCfg(C.Structure):
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
 
 
+class StftdRes(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32)]
+
+
+class StftdCfg(C.Structure):
+    _fields_ = [("n_res", C.c_int32), ("power_floor", C.c_float), ("log_floor", C.c_float)]
+
+
 _lib = None
 
 
@@ -212,6 +220,11 @@ def _declare(lib):
         "pk_gl_run": (C.c_int, [vp, vp, f32p, i32p, i32, i32, C.c_float, C.POINTER(C.c_uint64), f32p, f32p, i32]),
         "pk_gl_debug_read": (C.c_int, [vp, i32, f32p, i64]),
         "pk_istft_destroy": (None, [vp]),
+        "pk_stftd_create": (C.c_int, [vp, C.POINTER(StftdCfg), C.POINTER(StftdRes), f32p, C.POINTER(vp)]),
+        "pk_stftd_num_frames": (C.c_int, [vp, i32, i32, i32p]),
+        "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),
+        "pk_stftd_magnitude": (C.c_int, [vp, i32, f32p, i32p, i32, f32p, i32]),
+        "pk_stftd_destroy": (None, [vp]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),
