@@ -797,6 +797,87 @@ int pk_op_matmul(pk_ctx* ctx, const float* x, int32_t M, int32_t K, int32_t N, c
 int pk_op_expand(pk_ctx* ctx, const float* encodings, const int64_t* durations, int32_t B, int32_t T, int32_t C,
                  int32_t t_dec, float* out);
 
+/* ------------------------------------------ the engine's shared GEMMs exactly as the models launch them */
+/* These three run the kernels every dense layer of every model goes through (the implicit-conv tile GEMM with its
+ * split-fp16 variant and its row-maximum pass, and the few-rows GEMM of the autoregressive decoders) with every
+ * feature of their internal argument blocks, so that they can be compared with a reference at their own edges.
+ * Activations, residuals, row arrays and outputs are DEVICE pointers; weights, biases, cscale / cshift, the projection,
+ * the LayerNorm parameters and the stop vector are HOST arrays, [K][N] row-major, packed per call (so the calls are
+ * synchronous).  A field that is NULL / 0 switches its feature off. */
+typedef struct pk_op_gemm_cfg {
+    /* device */
+    const float* A;            /* [M][lda] rows of the timeline; rows outside [0, M) that taps or tile tails read are
+                                  supplied as zeros by the call (it copies A into a buffer with that margin) */
+    const float* A2;           /* [M][lda2], Cin2 more input channels appended to K, or NULL */
+    const float* res;          /* [M][ldr] */
+    const float* a_amax;       /* [M] max|A[r, 0..Cin)| or an upper bound of it, or NULL: computed by the launcher */
+    const float* a2_amax;      /* [M] likewise for A2 */
+    const int32_t* rowvalid;   /* [M], < 0: gap row */
+    const int32_t* out_rowmap; /* [M], < 0: row not stored */
+    float* C;                  /* [rows][ldc]; N columns are written (N / 2 under PK gate epilogue 1) */
+    float* C2;                 /* [M][ldc2]: columns >= nsplit */
+    /* host */
+    const float* W;            /* [wtaps * Cin + Cin2][N]; gate epilogues: columns [content (N/2) | gate (N/2)] */
+    const float* bias;         /* [N] (same column order as W) */
+    const float* cscale;       /* [N] */
+    const float* cshift;       /* [N] */
+    const float* W2;           /* epilogue 2: the [64][128] projection */
+    const float* bias2;        /* [128] */
+    int64_t tap_off[12];       /* ntaps > 0: tap t reads A + tap_off[t] (floats) + r * lda ... */
+    int32_t tap_w[12];         /* ... against the weight rows of packed tap tap_w[t] */
+    int32_t M, N, Cin;
+    int32_t taps, pad;         /* ntaps == 0: tap t reads row r + t - pad (wtaps = taps) */
+    int32_t ntaps, wtaps;      /* ntaps > 0: the explicit form above; wtaps = taps held by W */
+    int32_t Cin2, w2_slab0;    /* w2_slab0 = first weight row of the A2 block / 16 (even) */
+    int32_t lda, lda2, ldr, ldc, ldc2;
+    int32_t math;              /* 0 exact fp32, 1 split fp16 (falls back to fp32 below K = 128) */
+    int32_t tile;              /* split fp16: 0 = the launcher's rule, 64, 128 rows per workgroup */
+    int32_t act;               /* 0 none, 1 ReLU, 2 tanh */
+    int32_t epi;               /* 0 standard, 1 gate: tanh(content) * sigmoid(gate), 2 gate + projection (N == 128) */
+    int32_t res_pos;           /* 0 after the activation, 1 after the affine, 2 before the activation */
+    int32_t nsplit, acc2;
+    int32_t kernel;            /* OUT: 0 = k_gemm (fp32), 1 = k_gemm_h3 with 64-row tiles, 2 = with 128-row tiles */
+} pk_op_gemm_cfg;
+/* cfg is not const: the call writes cfg->kernel. */
+int pk_op_gemm(pk_ctx* ctx, pk_op_gemm_cfg* cfg);
+
+typedef struct pk_op_rowgemm_cfg {
+    /* device */
+    const float* x;            /* [M][ldx] */
+    const float* res;          /* [M][ldr] */
+    float* y;                  /* [M][ldy] */
+    float* lstm_c;             /* [M][lstm_H], updated in place; switches the LSTM-cell epilogue on */
+    float* lstm_h1;            /* [M][lstm_ld1] */
+    float* lstm_h2;            /* [M][lstm_ld2] */
+    const uint64_t* drop_seeds;   /* [M] */
+    const int32_t* stop_minlen;   /* [M] */
+    const int32_t* stop_maxlen;   /* [M] */
+    float* stop_probs;
+    int32_t* stop_len;         /* [M] */
+    int32_t* stop_ndone;       /* [1] */
+    /* host */
+    const float* W;            /* [K][N]; LSTM: columns [i (H) | f (H) | g (H) | o (H)] */
+    const float* bias;         /* [N] */
+    const float* ln_g;         /* [K] LayerNorm weight / bias of the prologue */
+    const float* ln_b;
+    const float* stop_w;       /* [K]: switches the stop-token head on */
+    uint64_t drop_base;
+    int32_t M, K, N, ldx, ldr, ldy;
+    int32_t act;               /* 0 none, 1 ReLU */
+    float ln_eps;
+    int32_t lstm_H, lstm_ld1, lstm_ld2;
+    int32_t dropout, drop_J, drop_j;
+    uint32_t drop_thr;         /* keep <=> word >= drop_thr */
+    float drop_scale;
+    float stop_bias, stop_thr;
+    int32_t stop_kind, stop_max_steps, stop_step;
+} pk_op_rowgemm_cfg;
+int pk_op_rowgemm(pk_ctx* ctx, const pk_op_rowgemm_cfg* cfg);
+
+/* amax[r] = max|A[r, 0..C)| for r0 <= r < r1 (device pointers; rows r0..r1-1 of both must exist, r0 may be negative).
+ * Asynchronous on the context's stream. */
+int pk_op_row_amax(pk_ctx* ctx, const float* A, int64_t lda, int32_t C, int64_t r0, int64_t r1, float* amax);
+
 #ifdef __cplusplus
 }
 #endif

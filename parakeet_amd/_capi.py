@@ -112,6 +112,28 @@ class StftdCfg(C.Structure):
     _fields_ = [("n_res", C.c_int32), ("power_floor", C.c_float), ("log_floor", C.c_float)]
 
 
+class OpGemmCfg(C.Structure):
+    """pk_op_gemm_cfg"""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "res", "a_amax", "a2_amax", "rowvalid", "out_rowmap", "C", "C2",
+                                           "W", "bias", "cscale", "cshift", "W2", "bias2")] +
+                [("tap_off", C.c_int64 * 12), ("tap_w", C.c_int32 * 12)] +
+                [(n, C.c_int32) for n in ("M", "N", "Cin", "taps", "pad", "ntaps", "wtaps", "Cin2", "w2_slab0", "lda", "lda2",
+                                          "ldr", "ldc", "ldc2", "math", "tile", "act", "epi", "res_pos", "nsplit", "acc2",
+                                          "kernel")])
+
+
+class OpRowgemmCfg(C.Structure):
+    """pk_op_rowgemm_cfg"""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "res", "y", "lstm_c", "lstm_h1", "lstm_h2", "drop_seeds", "stop_minlen",
+                                           "stop_maxlen", "stop_probs", "stop_len", "stop_ndone", "W", "bias", "ln_g", "ln_b",
+                                           "stop_w")] +
+                [("drop_base", C.c_uint64)] +
+                [(n, C.c_int32) for n in ("M", "K", "N", "ldx", "ldr", "ldy", "act")] + [("ln_eps", C.c_float)] +
+                [(n, C.c_int32) for n in ("lstm_H", "lstm_ld1", "lstm_ld2", "dropout", "drop_J", "drop_j")] +
+                [("drop_thr", C.c_uint32), ("drop_scale", C.c_float), ("stop_bias", C.c_float), ("stop_thr", C.c_float)] +
+                [(n, C.c_int32) for n in ("stop_kind", "stop_max_steps", "stop_step")])
+
+
 _lib = None
 
 
@@ -234,6 +256,9 @@ def _declare(lib):
         "pk_op_conv1d_cell_step": (C.c_int, [vp, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, f32p]),
         "pk_op_conv1d_batchnorm_nlc": (C.c_int, [vp, f32p, i32, i32, i32, i32, i32, i32, f32p, f32p, f32p, f32p,
                                                  f32p, f32p, C.c_float, f32p]),
+        "pk_op_gemm": (C.c_int, [vp, C.POINTER(OpGemmCfg)]),
+        "pk_op_rowgemm": (C.c_int, [vp, C.POINTER(OpRowgemmCfg)]),
+        "pk_op_row_amax": (C.c_int, [vp, f32p, i64, i32, i64, i64, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it

@@ -604,8 +604,9 @@ int pk_row_amax_launch(pk_ctx* ctx, const float* A, long lda, int C, long r0, lo
     return PK_OK;
 }
 
-int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& in) {
+int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& in, int* ran) {
     pk_gemm_args a = in;
+    if (a.tile != 0 && a.tile != 64 && a.tile != 128) PK_FAIL(PK_EINVAL, "GEMM: tile must be 0, 64 or 128 (got %d)", a.tile);
     if (a.Cin % BK != 0 || a.Cin2 % BK != 0)
         PK_FAIL(PK_EUNSUPPORTED, "GEMM: input channels (%d, %d) must be multiples of %d", a.Cin, a.Cin2, BK);
     if (a.M <= 0 || a.N <= 0) PK_FAIL(PK_EINVAL, "GEMM: empty problem");
@@ -625,6 +626,7 @@ int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& in) {
             a.tap_w[t] = t;
         }
         a.wslabs_total = a.taps * a.Cin / bk + a.Cin2 / bk;
+        if (h3) a.w2_slab0 /= 2;   // given in units of 16, like the explicit form below
     } else if (h3) {
         // callers give slab bookkeeping in units of 16; the split kernel uses slabs of 32
         a.w2_slab0 /= 2;
@@ -674,15 +676,19 @@ int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& in) {
         static const double small_factor = pk_prof_env("PK_GEMM_SMALL_FACTOR") ? atof(pk_prof_env("PK_GEMM_SMALL_FACTOR")) : 0.7;
         const double t1 = small_factor * (double)((wg1 + slots3 - 1) / slots3);   // half-size tiles, 3 per CU share the pipes
         static const int force = pk_prof_env("PK_GEMM_TILE") ? atoi(pk_prof_env("PK_GEMM_TILE")) : 0;   // 64 / 128: measurement override
-        if (force == 64 || (force != 128 && t1 < t2)) {
+        const int tile = force ? force : a.tile;   // the caller's choice (pk_gemm_args::tile) unless the profile build overrides it
+        if (tile == 64 || (tile != 128 && t1 < t2)) {
             dim3 g1((a.M + 63) / 64, grid.y);
             PK_LAUNCH(ctx, nm.c_str(), k_gemm_h3<1>, g1, dim3(256), 0, a);
+            if (ran) *ran = PK_GEMM_RAN_H3_64;
         } else {
             PK_LAUNCH(ctx, nm.c_str(), k_gemm_h3<2>, grid, dim3(256), 0, a);
+            if (ran) *ran = PK_GEMM_RAN_H3_128;
         }
         return PK_OK;
     }
     if (!a.Wp) PK_FAIL(PK_EINVAL, "GEMM: fp32 weights missing");
     PK_LAUNCH(ctx, prof_name, k_gemm<1>, grid, dim3(256), 0, a);
+    if (ran) *ran = PK_GEMM_RAN_F32;
     return PK_OK;
 }

@@ -2,6 +2,7 @@
 //   sinusoid_position_encoding   parakeet/modules/positional_encoding.py:20-39
 //   scaled_dot_product_attention parakeet/modules/attention.py:22-58 (float mask, returns the weights)
 //   Conv1dBatchNorm.forward      parakeet/modules/conv.py:186-260 (eval mode, NLC layout)
+// and, at the end, the engine's shared GEMMs (gemm.hip, rowgemm.hip) exactly as the models launch them.
 // Not on the FastSpeech2/PWG/WaveFlow path; they serve the other models' inference code.
 #include <algorithm>
 #include <cmath>
@@ -9,6 +10,7 @@
 
 #include "pk_gemm.h"
 #include "pk_philox.h"
+#include "pk_rowgemm.h"
 
 namespace {
 
@@ -377,4 +379,250 @@ extern "C" int pk_op_conv1d_cell_step(pk_ctx* ctx, float* buffer, const float* x
     PK_LAUNCH(ctx, "cell_out", k_cell_out, dim3(pk_div_up((long)B * Cout, 4)), dim3(256), 0, in, weight, bias, B, Cin, Cout, k,
               dilation, r, y);
     return PK_OK;
+}
+
+// ------------------------------------------------------------------ the shared GEMMs as the models launch them
+namespace {
+// dst row r (r_lo <= r < r_hi, dst points at row 0) = src row r for 0 <= r < M, zeros elsewhere; `ld` floats per row
+__global__ void k_copy_rows_margin(const float* __restrict__ src, int M, int ld, long r_lo, float* __restrict__ dst) {
+    const long r = r_lo + blockIdx.x;
+    const bool in = r >= 0 && r < M;
+    for (int c = threadIdx.x; c < ld; c += blockDim.x) dst[r * ld + c] = in ? src[r * ld + c] : 0.f;
+}
+
+static void op_permute_cols(const float* in, int K, int N, const std::vector<int>& perm, std::vector<float>& out) {
+    out.resize((size_t)K * N);
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < N; ++n) out[(size_t)k * N + n] = in[(size_t)k * N + perm[n]];
+}
+}  // namespace
+
+extern "C" int pk_op_gemm(pk_ctx* ctx, pk_op_gemm_cfg* c) {
+    if (!ctx || !c || !c->A || !c->W || !c->C) PK_FAIL(PK_EINVAL, "pk_op_gemm: NULL argument");
+    if (c->M <= 0 || c->N <= 0 || c->Cin <= 0 || c->Cin2 < 0 || c->lda < c->Cin || (c->A2 && c->lda2 < c->Cin2))
+        PK_FAIL(PK_EINVAL, "pk_op_gemm: bad shape");
+    if (c->Cin % PK_GEMM_BK != 0 || c->Cin2 % PK_GEMM_BK != 0)
+        PK_FAIL(PK_EUNSUPPORTED, "pk_op_gemm: input channels (%d, %d) must be multiples of %d", c->Cin, c->Cin2, PK_GEMM_BK);
+    const bool expl = c->ntaps > 0;
+    const int ntaps = expl ? c->ntaps : c->taps, wtaps = expl ? c->wtaps : c->taps;
+    if (ntaps <= 0 || wtaps <= 0) PK_FAIL(PK_EINVAL, "pk_op_gemm: no taps");
+    if (ntaps > PK_GEMM_MAX_TAPS || wtaps > PK_GEMM_MAX_TAPS)
+        PK_FAIL(PK_EUNSUPPORTED, "pk_op_gemm: more than %d taps", PK_GEMM_MAX_TAPS);
+    if (c->Cin2 > 0 && !c->A2) PK_FAIL(PK_EINVAL, "pk_op_gemm: Cin2 without A2");
+    if (c->Cin2 > 0 && (c->w2_slab0 < 0 || c->w2_slab0 * PK_GEMM_BK + c->Cin2 > wtaps * c->Cin + c->Cin2 || c->w2_slab0 % 2 != 0))
+        PK_FAIL(PK_EINVAL, "pk_op_gemm: w2_slab0 outside the weight (or odd)");
+    if (expl)
+        for (int t = 0; t < ntaps; ++t)
+            if (c->tap_w[t] < 0 || c->tap_w[t] >= wtaps) PK_FAIL(PK_EINVAL, "pk_op_gemm: tap_w[%d] outside the weight", t);
+    if (c->nsplit > 0 && !c->C2) PK_FAIL(PK_EINVAL, "pk_op_gemm: nsplit needs C2");
+    if (c->epi == PK_EPI_GATE_PROJ && (!c->W2)) PK_FAIL(PK_EINVAL, "pk_op_gemm: the projection epilogue needs W2");
+    PK_DEVICE(ctx->device);
+    const int K = wtaps * c->Cin + c->Cin2, N = c->N;
+    const bool gate = c->epi == PK_EPI_GATE || c->epi == PK_EPI_GATE_PROJ;
+    // ---- weights: [K][N] -> (gate column order) -> both packed forms
+    std::vector<float> wperm, bperm, packed, packed2f;
+    std::vector<uint16_t> packed_h, packed_h2;
+    const float* w = c->W;
+    const float* bias = c->bias;
+    if (gate && N % 128 == 0) {   // (any other N is refused by the launcher)
+        pk_gemm_gate_permute(c->W, K, N / 2, wperm);
+        w = wperm.data();
+        if (bias) {
+            pk_gemm_gate_permute_bias(c->bias, N / 2, bperm);
+            bias = bperm.data();
+        }
+    }
+    pk_gemm_pack(w, K, N, packed);
+    const bool split = c->math == PK_GEMM_MATH_F16X3 && c->Cin % PK_GEMM_HBK == 0 && c->Cin2 % PK_GEMM_HBK == 0;
+    if (split) pk_gemm_pack_h3(w, K, N, packed_h);
+    if (c->epi == PK_EPI_GATE_PROJ) pk_gemm_pack_h3(c->W2, 64, 128, packed_h2);
+    // ---- rows the kernels may read: [lo, rows_pad + hi) around the M given ones
+    const long rows_pad = (long)((c->M + PK_GEMM_BM - 1) / PK_GEMM_BM) * PK_GEMM_BM;
+    long lo = 0, hi = 0;
+    pk_gemm_args g;
+    if (expl) {
+        g.ntaps = ntaps;
+        for (int t = 0; t < ntaps; ++t) {
+            g.tap_off[t] = c->tap_off[t];
+            g.tap_w[t] = c->tap_w[t];
+            const long o = c->tap_off[t];
+            const long fl = o >= 0 ? o / c->lda : -((-o + c->lda - 1) / c->lda);
+            lo = std::min(lo, fl);
+            hi = std::max(hi, fl + 1);   // + 1: an offset that is no whole number of rows reaches into the next one
+        }
+        g.wslabs_total = K / PK_GEMM_BK;
+    } else {
+        if (c->pad < 0) PK_FAIL(PK_EINVAL, "pk_op_gemm: negative pad");
+        g.taps = c->taps;
+        g.pad = c->pad;
+        lo = -(long)c->pad;
+        hi = std::max<long>(0, c->taps - 1 - c->pad);
+    }
+    g.w2_slab0 = c->w2_slab0;
+    const long nrows = rows_pad + hi - lo;
+    if (nrows * (long)c->lda > (1L << 30)) PK_FAIL(PK_EUNSUPPORTED, "pk_op_gemm: problem too large for this entry point");
+    pk_dbuf d_a, d_a2, d_am, d_am2, d_wp, d_wh, d_wh2, d_b, d_b2, d_cs, d_ch;
+    auto cleanup = [&]() {
+        d_a.release(); d_a2.release(); d_am.release(); d_am2.release(); d_wp.release(); d_wh.release(); d_wh2.release();
+        d_b.release(); d_b2.release(); d_cs.release(); d_ch.release();
+    };
+    int st = PK_OK;
+    if ((st = d_a.reserve((size_t)nrows * c->lda * 4)) != PK_OK ||
+        (st = pk_upload(ctx, d_wp, packed.data(), packed.size() * 4)) != PK_OK ||
+        (split && (st = pk_upload(ctx, d_wh, packed_h.data(), packed_h.size() * 2)) != PK_OK) ||
+        (!packed_h2.empty() && (st = pk_upload(ctx, d_wh2, packed_h2.data(), packed_h2.size() * 2)) != PK_OK) ||
+        (bias && (st = pk_upload(ctx, d_b, bias, (size_t)N * 4)) != PK_OK) ||
+        (c->bias2 && (st = pk_upload(ctx, d_b2, c->bias2, (size_t)128 * 4)) != PK_OK) ||
+        (c->cscale && (st = pk_upload(ctx, d_cs, c->cscale, (size_t)N * 4)) != PK_OK) ||
+        (c->cshift && (st = pk_upload(ctx, d_ch, c->cshift, (size_t)N * 4)) != PK_OK) ||
+        (c->Cin2 > 0 && (st = d_a2.reserve((size_t)rows_pad * c->lda2 * 4)) != PK_OK) ||
+        (c->a_amax && (st = d_am.reserve((size_t)nrows * 4)) != PK_OK) ||
+        (c->Cin2 > 0 && c->a2_amax && (st = d_am2.reserve((size_t)rows_pad * 4)) != PK_OK)) {
+        cleanup();
+        return st;
+    }
+    float* a0 = d_a.as<float>() - lo * c->lda;
+    hipLaunchKernelGGL(k_copy_rows_margin, dim3((unsigned)nrows), dim3(128), 0, ctx->stream, c->A, c->M, c->lda, lo, a0);
+    g.A = a0;
+    g.lda = c->lda;
+    if (c->Cin2 > 0) {
+        hipLaunchKernelGGL(k_copy_rows_margin, dim3((unsigned)rows_pad), dim3(128), 0, ctx->stream, c->A2, c->M, c->lda2, 0L,
+                           d_a2.as<float>());
+        g.A2 = d_a2.as<float>();
+        g.lda2 = c->lda2;
+        g.Cin2 = c->Cin2;
+    }
+    if (c->a_amax) {
+        float* am = d_am.as<float>() - lo;
+        hipLaunchKernelGGL(k_copy_rows_margin, dim3((unsigned)nrows), dim3(64), 0, ctx->stream, c->a_amax, c->M, 1, lo, am);
+        g.a_amax = am;
+    }
+    if (c->Cin2 > 0 && c->a2_amax) {
+        hipLaunchKernelGGL(k_copy_rows_margin, dim3((unsigned)rows_pad), dim3(64), 0, ctx->stream, c->a2_amax, c->M, 1, 0L,
+                           d_am2.as<float>());
+        g.a2_amax = d_am2.as<float>();
+    }
+    g.Wp = d_wp.as<float>();
+    g.Wh = split ? d_wh.p : nullptr;
+    g.Wh2 = packed_h2.empty() ? nullptr : d_wh2.p;
+    g.math = c->math;
+    g.tile = c->tile;
+    g.bias = bias ? d_b.as<float>() : nullptr;
+    g.bias2 = c->bias2 ? d_b2.as<float>() : nullptr;
+    g.cscale = c->cscale ? d_cs.as<float>() : nullptr;
+    g.cshift = c->cshift ? d_ch.as<float>() : nullptr;
+    g.res = c->res;
+    g.ldr = c->ldr;
+    g.res_pos = c->res_pos;
+    g.C = c->C;
+    g.ldc = c->ldc;
+    g.rowvalid = c->rowvalid;
+    g.out_rowmap = c->out_rowmap;
+    g.M = c->M;
+    g.N = N;
+    g.Cin = c->Cin;
+    g.act = c->act;
+    g.epi = c->epi;
+    g.nsplit = c->nsplit;
+    g.C2 = c->C2;
+    g.ldc2 = c->ldc2;
+    g.acc2 = c->acc2;
+    int ran = -1;
+    st = pk_gemm_launch(ctx, "op_gemm", g, &ran);
+    c->kernel = ran;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == PK_OK) {   // (the copies above are in flight either way)
+        pk_set_error("pk_op_gemm: stream sync failed");
+        st = PK_EHIP;
+    }
+    cleanup();
+    return st;
+}
+
+extern "C" int pk_op_rowgemm(pk_ctx* ctx, const pk_op_rowgemm_cfg* c) {
+    if (!ctx || !c || !c->x || !c->W || (!c->y && !c->lstm_c)) PK_FAIL(PK_EINVAL, "pk_op_rowgemm: NULL argument");
+    if (c->M > 0 && c->N > 0 && c->K > 0 && c->ldx < c->K)
+        PK_FAIL(PK_EINVAL, "pk_op_rowgemm: ldx < K");
+    PK_DEVICE(ctx->device);
+    pk_rowgemm_args a;
+    std::vector<float> wperm, bperm, packed;
+    pk_dbuf d_w, d_b, d_g, d_lb, d_sw;
+    auto cleanup = [&]() { d_w.release(); d_b.release(); d_g.release(); d_lb.release(); d_sw.release(); };
+    int st = PK_OK;
+    const bool shaped = c->M > 0 && c->N > 0 && c->K > 0;   // (an empty problem goes to the launcher for its status)
+    if (shaped) {
+        const float* w = c->W;
+        const float* bias = c->bias;
+        if (c->lstm_c && c->N == 4 * c->lstm_H && c->lstm_H % 4 == 0) {   // (anything else is refused by the launcher)
+            std::vector<int> perm;
+            pk_rowgemm_lstm_perm(c->lstm_H, perm);
+            op_permute_cols(c->W, c->K, c->N, perm, wperm);
+            w = wperm.data();
+            if (bias) {
+                op_permute_cols(c->bias, 1, c->N, perm, bperm);
+                bias = bperm.data();
+            }
+        }
+        pk_rowgemm_pack(w, c->K, c->N, packed);
+        if ((st = pk_upload(ctx, d_w, packed.data(), packed.size() * 4)) != PK_OK ||
+            (bias && (st = pk_upload(ctx, d_b, bias, (size_t)c->N * 4)) != PK_OK) ||
+            (c->ln_g && (st = pk_upload(ctx, d_g, c->ln_g, (size_t)c->K * 4)) != PK_OK) ||
+            (c->ln_b && (st = pk_upload(ctx, d_lb, c->ln_b, (size_t)c->K * 4)) != PK_OK) ||
+            (c->stop_w && (st = pk_upload(ctx, d_sw, c->stop_w, (size_t)c->K * 4)) != PK_OK)) {
+            cleanup();
+            return st;
+        }
+        a.Wt = d_w.as<float>();
+        a.bias = bias ? d_b.as<float>() : nullptr;
+        a.ln_g = c->ln_g ? d_g.as<float>() : nullptr;
+        a.ln_b = c->ln_b ? d_lb.as<float>() : nullptr;
+        a.stop_w = c->stop_w ? d_sw.as<float>() : nullptr;
+    }
+    a.x = c->x;
+    a.ldx = c->ldx;
+    a.res = c->res;
+    a.ldr = c->ldr;
+    a.y = c->y;
+    a.ldy = c->ldy;
+    a.M = c->M;
+    a.K = c->K;
+    a.N = c->N;
+    a.act = c->act;
+    a.ln_eps = c->ln_eps;
+    a.lstm_c = c->lstm_c;
+    a.lstm_H = c->lstm_H;
+    a.lstm_h1 = c->lstm_h1;
+    a.lstm_ld1 = c->lstm_ld1;
+    a.lstm_h2 = c->lstm_h2;
+    a.lstm_ld2 = c->lstm_ld2;
+    a.dropout = c->dropout;
+    a.drop_base = c->drop_base;
+    a.drop_J = c->drop_J;
+    a.drop_j = c->drop_j;
+    a.drop_seeds = reinterpret_cast<const unsigned long long*>(c->drop_seeds);
+    a.drop_thr = c->drop_thr;
+    a.drop_scale = c->drop_scale;
+    a.stop_bias = c->stop_bias;
+    a.stop_thr = c->stop_thr;
+    a.stop_kind = c->stop_kind;
+    a.stop_max_steps = c->stop_max_steps;
+    a.stop_step = c->stop_step;
+    a.stop_minlen = c->stop_minlen;
+    a.stop_maxlen = c->stop_maxlen;
+    a.stop_probs = c->stop_probs;
+    a.stop_len = c->stop_len;
+    a.stop_ndone = c->stop_ndone;
+    st = pk_rowgemm_launch(ctx, "op_rowgemm", a);
+    if (shaped && hipStreamSynchronize(ctx->stream) != hipSuccess && st == PK_OK) {
+        pk_set_error("pk_op_rowgemm: stream sync failed");
+        st = PK_EHIP;
+    }
+    cleanup();
+    return st;
+}
+
+extern "C" int pk_op_row_amax(pk_ctx* ctx, const float* A, int64_t lda, int32_t C, int64_t r0, int64_t r1, float* amax) {
+    if (!ctx || !A || !amax) PK_FAIL(PK_EINVAL, "pk_op_row_amax: NULL argument");
+    if (C <= 0 || lda < C) PK_FAIL(PK_EINVAL, "pk_op_row_amax: bad shape");
+    PK_DEVICE(ctx->device);
+    return pk_row_amax_launch(ctx, A, lda, C, r0, r1, amax);
 }

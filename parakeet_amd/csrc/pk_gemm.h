@@ -21,6 +21,8 @@ enum { PK_RES_AFTER_ACT = 0, PK_RES_AFTER_AFFINE = 1, PK_RES_BEFORE_ACT = 2 };
 // C[r, n] = epilogue( sum_{tap, ci} A[r + tap - pad, ci] * W[tap*Cin + ci, n] )
 //   epilogue: v += bias[n]; v = act(v); v += res[r, n]; v = rowvalid[r] ? v : 0;
 //             v = v * cscale[n] + cshift[n]; store to C[out_rowmap ? out_rowmap[r] : r, n]
+//             (PK_RES_AFTER_ACT, the default: the affine comes AFTER the gap test, so with cscale set a gap row
+//             stores cshift[n], not 0; cshift is applied only together with cscale)
 //   res_pos moves the residual: PK_RES_AFTER_AFFINE  v = rowvalid ? act(v + bias) * cscale + cshift + res : 0
 //                               (x + BatchNorm(ReLU(conv(x))), SpeedySpeech's ResidualBlock)
 //                               PK_RES_BEFORE_ACT    v = rowvalid ? act(v + bias + res) * cscale + cshift : 0
@@ -79,7 +81,13 @@ struct pk_gemm_args {
     const float* a_amax = nullptr;
     const float* a2_amax = nullptr;
     int tap_row[PK_GEMM_MAX_TAPS] = {0};
+    // rows per workgroup of the split-fp16 kernel: 0 = the launcher's occupancy rule, 64 / 128 = that tile (every output
+    // element sees the same scales and the same sequence of products either way, so the two results are bit-equal, which
+    // tests/test_gemm_sweep_gpu.py asserts; tests reach k_gemm_h3<2> at small shapes this way)
+    int tile = 0;
 };
+
+enum { PK_GEMM_RAN_F32 = 0, PK_GEMM_RAN_H3_64 = 1, PK_GEMM_RAN_H3_128 = 2 };
 
 // max|A[r, 0..C)| for r0 <= r < r1 into amax[r] (amax indexed like the rows of A); on ctx->stream
 int pk_row_amax_launch(pk_ctx* ctx, const float* A, long lda, int C, long r0, long r1, float* amax);
@@ -97,4 +105,5 @@ void pk_conv_to_kn(const float* w, int Cout, int Cin, int k, std::vector<float>&
 void pk_gemm_gate_permute(const float* Wkn, int K, int Cz, std::vector<float>& out);
 void pk_gemm_gate_permute_bias(const float* b, int Cz, std::vector<float>& out);
 
-int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& a);
+// ran (optional): which kernel was launched, PK_GEMM_RAN_*
+int pk_gemm_launch(pk_ctx* ctx, const char* prof_name, const pk_gemm_args& a, int* ran = nullptr);

@@ -144,3 +144,211 @@ def mutants(A, W, y):
     m[last] = 0.0
     out["row"] = m
     return out
+
+
+# ------------------------------------------------------------------------------------------------ split-fp16 GEMM
+# Format constants of csrc/pk_split.h: a block maximum is brought to [2^BLK_TOP, 2^(BLK_TOP + 1)); fp32 exponent fields
+# below EXP_MIN / above EXP_MAX are clamped (blocks below 2^-40 are scaled as if they were 2^-40).
+BLK_TOP, EXP_MIN, EXP_MAX = 13, 87, 200
+U16 = 2.0 ** -11        # unit roundoff of IEEE binary16 (11-bit significand), round to nearest
+SUB16 = 2.0 ** -25      # half the spacing 2^-24 of binary16 subnormals: absolute rounding error below 2^-14
+
+
+def act_scale(amax):
+    """2^kx the kernel multiplies an activation block with, from the block maximum it is GIVEN (blk_scale_exp: the fp32
+    exponent field e of the maximum, clamped to [EXP_MIN, EXP_MAX], kx = BLK_TOP + 127 - e).  Exact, like the kernel."""
+    a = np.asarray(amax, dtype=np.float32)
+    e = (a.view(np.uint32) >> np.uint32(23)).astype(np.int64) & 0xFF
+    return np.ldexp(1.0, BLK_TOP + 127 - np.clip(e, EXP_MIN, EXP_MAX))
+
+
+def weight_scale(wmax):
+    """2^kw of a 128-column weight block (pk_weight_scale_exp): wmax * 2^kw in [2^13, 2^14), |kw| <= 40, 1 for a zero block."""
+    w = np.asarray(wmax, dtype=np.float64)
+    _, e = np.frexp(w)
+    return np.where(w == 0, 1.0, np.ldexp(1.0, np.clip(14 - e, -40, 40)))
+
+
+def split_dot_bound(absprod, K, sum_abs_a, sum_abs_w, sa, sw, bias=None):
+    """Error of sum_k a_k w_k evaluated as a_hi w_hi + a_lo w_hi + a_hi w_lo on fp16 parts of the SCALED operands
+    x = sa * a, v = sw * w (sa (M, 1) = act_scale of the row's block, sw (1, N) = weight_scale of the column's block),
+    fp32 accumulation, exact unscaling by 1 / (sa * sw).
+
+    Parts: hi = fp16(x) has |x - hi| <= U16 |x| (or <= SUB16 where hi is subnormal); x - hi is exact in fp32 (a multiple
+    of ulp32(x) below ulp16(x)); lo = fp16(x - hi) has error <= U16 |x - hi| <= U16^2 |x| = 2^-22 |x| where lo is normal and
+    <= SUB16 where it is subnormal.  So e_x = |x - hi - lo| <= 2^-22 |x| + 2^-25, and the same for v.
+    Products: hi*hi + lo*hi + hi*lo = (x - e_x)(v - e_v) - lo_x lo_v, i.e. per term an error
+        e_x |v| + |x| e_v + e_x e_v + |lo_x lo_v|,   |lo_x| <= U16 (1 + U16) |x| + SUB16  (same for v)
+    Summed over k in scaled units, with P = sum |x||v|, SX = sum |x|, SV = sum |v|:
+        rep = (3 * 2^-22 (1 + 2^-9)) P + 2^-25 (1 + 2^-9) (SX + SV) + K 2^-49
+    (2^-22 P twice for e_x |v| and |x| e_v, once for lo*lo; the factor (1 + 2^-9) and K 2^-49 absorb every second-order
+    product of the above: 2^-44 P, 2^-36 (SX + SV) from lo*lo's and e_x e_v's cross terms, 2^-50 K twice).
+    Each fp16 x fp16 product has 22 significant bits: exact in fp32.  Accumulation: 3K terms + bias in any order,
+    gamma_(3K+2) under the C_MFMA allowance, on sum |parts' products| <= (|hi_x| + |lo_x|)(|hi_v| + |lo_v|) summed,
+    |hi| + |lo| <= (1 + 2^-10 + 2^-21)|x| + 2^-24: <= (1 + 2^-9) P + 2^-23 (SX + SV) + K 2^-48.
+    Unscaled: P / (sa sw) = |a|.|w| = absprod, SX / (sa sw) = sum|a| / sw, SV / (sa sw) = sum|w| / sa -- the floor terms
+    scale with (block maximum of the row) * sum|w| and (block maximum of the column) * sum|a|, as 1 / sa <= amax 2^-13."""
+    P = np.asarray(absprod, dtype=np.float64)
+    sa = np.asarray(sa, dtype=np.float64)
+    sw = np.asarray(sw, dtype=np.float64)
+    floor_sum = np.asarray(sum_abs_a, np.float64) / sw + np.asarray(sum_abs_w, np.float64) / sa
+    unit = 1.0 / (sa * sw)
+    g = 1.0 + 2.0 ** -9
+    rep = 3.0 * 2.0 ** -22 * g * P + SUB16 * g * floor_sum + K * 2.0 ** -49 * unit
+    mag = g * P + 2.0 ** -23 * floor_sum + K * 2.0 ** -48 * unit
+    if bias is not None:
+        mag = mag + np.abs(np.asarray(bias, dtype=np.float64))
+    return rep + C_MFMA * (3 * K + 2) * U * mag
+
+
+# __expf(x) = exp2(x * log2(e)).  ROCm's documentation on this machine states no error for it; this is the derivation
+# from the instruction: v_exp_f32 is 1 ulp (2u relative); its argument t = x * log2(e) carries the rounding of the
+# constant and of the product (2u relative, |dt| <= 2u |t|), which exp2 turns into the relative error ln 2 * |dt| =
+# 2u |x|.  Results that underflow are flushed: an absolute 2^-126, nothing next to the u-sized terms around it.
+def fast_exp_rel(x):
+    return 2.0 * U * (np.abs(np.asarray(x, dtype=np.float64)) + 1.0)
+
+
+TANH_CLAMP = 10.0
+
+
+def gate_bound(ca, cb, b_ca, b_cb):
+    """z = tanh(ca) * sigmoid(cb) from pre-activations with absolute errors b_ca, b_cb, computed as
+    ea = __expf(-2 clamp(ca, +-10)), eb = __expf(-cb), z = (1 - ea) / ((1 + ea)(1 + eb)).
+    T = (1 - ea) / (1 + ea): dT/dca <= 1; dT/dea * ea = 2 ea / (1 + ea)^2 <= 1/2, so ea's relative error d_a costs d_a / 2;
+    the clamp changes tanh by at most 1 - tanh(10) where |ca| can reach 10.  S = 1 / (1 + eb): dS/dcb <= 1/4,
+    dS/deb * eb = S (1 - S) <= 1/4.  Roundings of 1 - ea, 1 + ea, 1 + eb, the product (u each) and the division (2u: not
+    assumed correctly rounded): 6u relative to z."""
+    ca, cb = np.asarray(ca, np.float64), np.asarray(cb, np.float64)
+    T, S = np.tanh(ca), 1.0 / (1.0 + np.exp(-cb))
+    clamp = np.where(np.abs(ca) + b_ca >= TANH_CLAMP, 1.0 - np.tanh(TANH_CLAMP), 0.0)
+    bT = b_ca + 0.5 * fast_exp_rel(2.0 * np.minimum(np.abs(ca) + b_ca, TANH_CLAMP)) + clamp
+    bS = 0.25 * b_cb + 0.25 * fast_exp_rel(np.abs(cb) + b_cb)
+    return np.abs(S) * bT + np.abs(T) * bS + bT * bS + 6.0 * U * np.abs(T * S)
+
+
+def epilogue_step(v, b, rounding=1):
+    """after an operation whose exact result is v from operands with propagated error b: + `rounding` roundings of it"""
+    return b + rounding * U * (np.abs(v) + b)
+
+
+# tanhf / expf of the device library: the documentation at hand states no error for them; the allowance is the 2 ulp = 4u
+# relative this file already grants expf (softmax_rel_bound) and logf (log_bound); |tanh| <= 1 makes it an absolute 4u.
+LIBM_REL = 4.0 * U
+
+
+def tanh_bound(x, b):
+    """|d tanh| <= 1 * b (derivative <= 1) + 4u"""
+    return b + LIBM_REL
+
+
+def sigmoid_bound(x, b):
+    """1 / (1 + expf(-x)): derivative <= 1/4; expf's relative error e acts as S (1 - S) e <= e / 4; 1 + . and 1 / . : 3u"""
+    return 0.25 * b + 0.25 * LIBM_REL + 3.0 * U
+
+
+def layernorm_bound(x, g, beta, eps):
+    """xn = (x - mean) * rstd * g + beta over the last axis (K) in fp32 -> (xn fp64, bound).
+    mean: K additions in any order and the product with the rounded 1/K: (K + 2) u mean|x|.  d = x - mean: b_d = b_mean +
+    u |d|.  var = mean(d^2): each square moves by 2 |d| b_d + b_d^2 (+ u d^2), the sum and 1/K add (K + 2) u var.
+    rstd = 1 / sqrt(var + eps): |d rstd / d var| = rstd^3 / 2, taken at the smallest variance the error allows; the
+    addition of eps, sqrtf and the division: 4u relative (sqrtf and the division are not assumed correctly rounded).
+    The three products and the addition of beta: 3u on the product, u on the sum."""
+    x = np.asarray(x, np.float64)
+    K = x.shape[-1]
+    mean = x.mean(-1, keepdims=True)
+    b_mean = (K + 2) * U * np.abs(x).mean(-1, keepdims=True)
+    d = x - mean
+    b_d = b_mean + U * np.abs(d)
+    var = (d * d).mean(-1, keepdims=True)
+    b_var = (2 * np.abs(d) * b_d + b_d ** 2 + U * d * d).mean(-1, keepdims=True) + (K + 2) * U * var
+    rstd = 1.0 / np.sqrt(var + eps)
+    rs_hi = 1.0 / np.sqrt(np.maximum(var - b_var, 0.0) + eps)
+    b_rs = 0.5 * rs_hi ** 3 * b_var + 4.0 * U * rs_hi
+    g, beta = np.asarray(g, np.float64), np.asarray(beta, np.float64)
+    core = d * rstd * g
+    b_core = np.abs(g) * (b_d * rstd + np.abs(d) * b_rs + b_d * b_rs) + 3.0 * U * np.abs(core)
+    xn = core + beta
+    return xn, b_core + U * (np.abs(xn) + b_core)
+
+
+def lstm_bound(gi, gf, gg, go, b_pre, c, b_c):
+    """One LSTMCell step from gate pre-activations (each with absolute error b_pre) and the cell state c (error b_c):
+    c' = sigmoid(f) c + sigmoid(i) tanh(g), h = sigmoid(o) tanh(c') -> (c', h, b_c', b_h).
+    Product rule with the derivative bounds of sigmoid_bound / tanh_bound; two products and a sum for c' (u each on its
+    operands: 3u (|f c| + |i g|)), tanhf(c') and a product for h."""
+    si, sf, so = (1.0 / (1.0 + np.exp(-np.asarray(v, np.float64))) for v in (gi, gf, go))
+    tg = np.tanh(np.asarray(gg, np.float64))
+    b_s, b_t = sigmoid_bound(None, b_pre), tanh_bound(None, b_pre)
+    c = np.asarray(c, np.float64)
+    cn = sf * c + si * tg
+    b_cn = (np.abs(c) * b_s + sf * b_c + b_s * b_c) + (np.abs(tg) * b_s + si * b_t + b_s * b_t)
+    b_cn = b_cn + 3.0 * U * (np.abs(sf * c) + np.abs(si * tg) + b_cn)
+    tc = np.tanh(cn)
+    b_tc = tanh_bound(None, b_cn)
+    h = so * tc
+    b_h = np.abs(tc) * b_s + so * b_tc + b_s * b_tc
+    return cn, h, b_cn, b_h + U * (np.abs(h) + b_h)
+
+
+def split_emulation(A, W, sa, sw):
+    """numpy emulation of the split product (for the CPU proof): scale, np.float16 hi / lo, three float32 products
+    accumulated in float32, exact unscale.  A (M, K) float32, W (K, N) float32, sa (M, 1), sw (1, N)."""
+    x = (A.astype(np.float64) * sa).astype(np.float32)
+    v = (W.astype(np.float64) * sw).astype(np.float32)
+    xh = x.astype(np.float16).astype(np.float32)
+    xl = (x - xh).astype(np.float16).astype(np.float32)
+    vh = v.astype(np.float16).astype(np.float32)
+    vl = (v - vh).astype(np.float16).astype(np.float32)
+    acc = xh @ vh + xl @ vh + xh @ vl
+    assert acc.dtype == np.float32
+    return (acc.astype(np.float64) / (sa * sw)).astype(np.float32)
+
+
+def _fp16_hi(x):
+    """x rounded to the fp16 grid of its own binade (a power-of-two block scale does not change it)"""
+    m, e = np.frexp(np.asarray(x, np.float64))
+    return np.ldexp(np.round(m * 2048.0) / 2048.0, e)
+
+
+def split_mutants(A, W, y, sa_own=None, sw=None, sa=None, slab=None):
+    """Wrong results specific to the split kernel, {name: wrong y} (y = A @ W in fp64, same shapes as mutants()):
+       lohi:     the lo*hi term of one 32-wide K slab (default: the middle one) is missing for the first 64-row tile
+                 (the activations' low parts of that slab dropped);
+       hilo:     the hi*lo term of that slab is missing for the first 128-column tile (the weights' low parts dropped);
+       ownscale: the row scale comes from the row itself (sa_own) instead of the rows its taps read (sa): where the
+                 neighbour is larger, scaled values overflow fp16 -- emulated, returned only when sa_own is given."""
+    A32, W32 = np.asarray(A, np.float32).astype(np.float64), np.asarray(W, np.float32).astype(np.float64)
+    K = A32.shape[1]
+    out = {}
+    k0 = (K // 32 // 2 if slab is None else slab) * 32
+    ks = slice(k0, k0 + 32)
+    wrong = y.copy()
+    wrong[:64] -= (A32[:64, ks] - _fp16_hi(A32[:64, ks])) @ _fp16_hi(W32[ks])
+    out["lohi"] = wrong
+    wrong = y.copy()
+    wrong[:, :128] -= _fp16_hi(A32[:, ks]) @ (W32[ks, :128] - _fp16_hi(W32[ks, :128]))
+    out["hilo"] = wrong
+    if sa_own is not None:
+        with np.errstate(over="ignore", invalid="ignore"):
+            out["ownscale"] = split_emulation(np.asarray(A, np.float32), np.asarray(W, np.float32), sa_own, sw).astype(np.float64)
+    return out
+
+
+def gemm_epilogue_mutants(want, res=None, gap_rows=None, c2_old=None, c2_new=None):
+    """(c) a gap row keeps its residual; (d) C2 overwritten where acc2 asks for += ."""
+    out = {}
+    if res is not None and gap_rows is not None and len(gap_rows):
+        m = want.copy()
+        m[gap_rows] = np.asarray(res, np.float64)[gap_rows]
+        out["gapres"] = m
+    if c2_old is not None:
+        out["c2over"] = np.asarray(c2_new, np.float64) - np.asarray(c2_old, np.float64)
+    return out
+
+
+def lstm_swap_mutant(W, H):
+    """(e) the i and f gate columns of every unit swapped: W (K, 4H) in [i | f | g | o] order -> wrong W"""
+    W = np.asarray(W).copy()
+    W[:, :H], W[:, H:2 * H] = np.asarray(W)[:, H:2 * H].copy(), np.asarray(W)[:, :H].copy()
+    return W

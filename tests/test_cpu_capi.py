@@ -71,6 +71,14 @@ def test_struct_sizes_match_header():
     assert C.sizeof(_capi.WfCfg) == 4 * (1 + 4 + 7)
     assert C.sizeof(_capi.TtsCfg) == 4 * (29 + 7 + 8)   # pk_tts_cfg: 29 int32 fields + 7 + 8 for the style encoder
     assert C.sizeof(_capi.TacoCfg) == 4 * 18 + 4     # pk_taco_cfg: 18 int32 fields + float p_prenet_dropout
+    assert C.sizeof(_capi.OpGemmCfg) == 8 * 15 + 8 * 12 + 4 * 12 + 4 * 22   # pointers, tap_off, tap_w, int32 fields
+    # pk_op_rowgemm_cfg: 17 pointers, drop_base, 21 four-byte fields, padded to 8
+    assert C.sizeof(_capi.OpRowgemmCfg) == 8 * 17 + 8 + 4 * 21 + 4
+    header = open(os.path.join(ROOT, "include", "pk_synth.h")).read()
+    for cls, name in ((_capi.OpGemmCfg, "pk_op_gemm_cfg"), (_capi.OpRowgemmCfg, "pk_op_rowgemm_cfg")):
+        body = re.sub(r"/\*.*?\*/", "", header.split("typedef struct " + name + " {")[1].split("} " + name)[0], flags=re.S)
+        declared = [n.split("[")[0] for stmt in body.split(";") for n in re.findall(r"[\s*]([A-Za-z_0-9\[\]]+)\s*(?:,|$)", stmt.strip())]
+        assert declared == [n for n, _ in cls._fields_], name
 
 
 def test_smoke_config_subset_is_valid():

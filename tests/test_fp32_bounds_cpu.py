@@ -121,6 +121,163 @@ def test_stft_mel_bounds(c):
             assert fb.ratio(wrong, r["spec"], r["b_spec"]) > 1.0
 
 
+@pytest.mark.parametrize("c", sc.GEMM_CASES + sc.GEMM_TAIL_CASES, ids=sc.gemm_id)
+def test_split_gemm_bounds(c):
+    """the split bound accepts the numpy emulation of the algorithm (block scale, float16 hi / lo, three products, float32
+    accumulation) and rejects the three standing mutants and the split kernel's own, for every case"""
+    p = sc.gemm_problem(c)
+    ref = sc.gemm_reference(p)
+    A, W, y, b = ref["Aim"], ref["Wim"], ref["pre"], ref["b_pre"]
+    emu = fb.split_emulation(A, W, ref["sa"], ref["sw"])
+    if c.bias:
+        emu = emu + p["bias"]
+    assert emu.dtype == np.float32 and fb.ratio(emu, y, b) <= 1.0
+    for name, wrong in {**fb.mutants(A, W, y), **fb.split_mutants(A, W, y, slab=p["loud"])}.items():
+        assert fb.ratio(wrong, y, b) > 1.0, f"the bound accepts the '{name}' mutant"
+    if c.taps > 1 and c.M > 8:
+        # (b) a row scaled by its own maximum, next to a neighbour 2^12 larger: its taps' values overflow fp16
+        A2 = p["A"].copy()
+        A2[1::2] *= np.float32(2.0 ** 12)
+        p2 = dict(p, A=A2)
+        r2 = sc.gemm_reference(p2)
+        _, _, _, _, own = sc.gemm_operands(p2)
+        wrong = fb.split_mutants(r2["Aim"], r2["Wim"], r2["pre"], fb.act_scale(own)[:, None], r2["sw"], r2["sa"])["ownscale"]
+        assert fb.ratio(wrong, r2["pre"] - (p["bias"] if c.bias else 0), r2["b_pre"]) > 1.0
+        emu2 = fb.split_emulation(r2["Aim"], r2["Wim"], r2["sa"], r2["sw"]) + (p["bias"] if c.bias else np.float32(0))
+        assert fb.ratio(emu2, r2["pre"], r2["b_pre"]) <= 1.0
+    if c.res and c.gaps:
+        # (c) a gap row that keeps its residual
+        gaps = sc.gemm_gap_rows(c.M)
+        for name, wrong in fb.gemm_epilogue_mutants(ref["C"], p["res"][:, :c.N], gaps).items():
+            assert fb.ratio(wrong, ref["C"], ref["b_C"]) > 1.0, name
+
+
+@pytest.mark.parametrize("c", sc.ROW_CASES, ids=sc.row_id)
+def test_rowgemm_plain_bounds(c):
+    x, w, b = sc.rowgemm_inputs(c.M, c.K, c.N, bias=c.bias)
+    want, _ = sc.matmul_reference(x, w, b)
+    A, W = x.astype(np.float64), w.astype(np.float64)
+    _check_stage("rowgemm", A, W, want, np.abs(A) @ np.abs(W), c.K, None if b is None else b.astype(np.float64))
+
+
+@pytest.mark.parametrize("K", sc.ROW_LN_K)
+def test_rowgemm_layernorm_bounds(K):
+    M, N = 31, 80
+    _, w, bias = sc.rowgemm_inputs(M, K, N, "lnw")
+    x, g, beta = sc.layernorm_rows(M, K)
+    want, bound, xn, b_xn = sc.rowgemm_ln_reference(x, g, beta, w, bias)
+    mean = x.sum(1, keepdims=True, dtype=np.float32) * np.float32(1.0 / K)
+    d = x - mean
+    rstd = np.float32(1.0) / np.sqrt((d * d).sum(1, keepdims=True, dtype=np.float32) * np.float32(1.0 / K) + np.float32(1e-5))
+    xn32 = d * rstd * g + beta
+    assert xn32.dtype == np.float32 and fb.ratio(xn32, xn, b_xn) <= 1.0
+    assert np.all(xn32[0] == beta) or fb.ratio(xn32[:1], xn[:1], b_xn[:1]) <= 1.0      # the constant row
+    assert fb.ratio(xn32 @ w + bias, want, bound) <= 1.0
+    for name, wrong in fb.mutants(xn, w.astype(np.float64), want).items():
+        assert fb.ratio(wrong, want, bound) > 1.0, name
+    # a prologue that divides by K + 1, or forgets eps (the constant row: 0 / 0), must be seen
+    assert fb.ratio(xn * np.sqrt((K + 1.0) / K), xn, b_xn) > 1.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d64 = x.astype(np.float64) - x.astype(np.float64).mean(1, keepdims=True)
+        no_eps = d64 / np.sqrt((d64 * d64).mean(1, keepdims=True)) * g + beta
+    assert fb.ratio(no_eps[:1], xn[:1], b_xn[:1]) > 1.0
+
+
+@pytest.mark.parametrize("H", sc.ROW_LSTM_H)
+def test_rowgemm_lstm_bounds(H):
+    M, K = 31, 64
+    r = sc.rng_for("lstm", H)
+    _, w, bias = sc.rowgemm_inputs(M, K, 4 * H, "lstmw")
+    x = sc.f32(r.normal(0.3, 1, (M, K)))
+    c0 = sc.f32(r.normal(0.2, 1, (M, H)))
+    cn, h, b_c, b_h = sc.lstm_reference(x, w, bias, c0.astype(np.float64))
+    pre = x @ w + bias
+    sig = lambda v: np.float32(1) / (np.float32(1) + np.exp(-v))
+    c32 = sig(pre[:, H:2 * H]) * c0 + sig(pre[:, :H]) * np.tanh(pre[:, 2 * H:3 * H])
+    h32 = sig(pre[:, 3 * H:]) * np.tanh(c32)
+    assert h32.dtype == np.float32 and fb.ratio(c32, cn, b_c) <= 1.0 and fb.ratio(h32, h, b_h) <= 1.0
+    # (e) the i and f gate columns of the units swapped
+    cw, hw, _, _ = sc.lstm_reference(x, fb.lstm_swap_mutant(w, H), fb.lstm_swap_mutant(bias[None], H)[0], c0.astype(np.float64))
+    assert fb.ratio(cw, cn, b_c) > 1.0 and fb.ratio(hw, h, b_h) > 1.0
+    for name, wrong in fb.mutants(x, w, pre.astype(np.float64)).items():               # through the cell: one gate of one unit
+        cm, hm, _, _ = fb.lstm_bound(wrong[:, :H], wrong[:, H:2 * H], wrong[:, 2 * H:3 * H], wrong[:, 3 * H:], 0.0, c0.astype(np.float64), 0.0)
+        assert max(fb.ratio(cm, cn, b_c), fb.ratio(hm, h, b_h)) > 1.0, name
+
+
+def _through_epilogue(p, ref, pre):
+    """largest error / bound of the outputs the epilogue makes of a product `pre`"""
+    e = sc.gemm_epilogue_reference(p, pre, np.zeros_like(ref["b_pre"]))
+    r = fb.ratio(e["C"], ref["C"], ref["b_C"])
+    return max(r, fb.ratio(e["C2"], ref["C2"], ref["b_C2"])) if "C2" in e else r
+
+
+@pytest.mark.parametrize("name,build", sc.GEMM_FEATURE_PROBLEMS, ids=[n for n, _ in sc.GEMM_FEATURE_PROBLEMS])
+def test_gemm_feature_problem_bounds(name, build):
+    """the problems of the feature tests of tests/test_gemm_sweep_gpu.py (gate, projection, nsplit, A2, skipped tap, mixed
+    magnitudes, given row maxima): what the epilogue makes of the emulated split product is inside the bound of the
+    OUTPUT, what it makes of every mutant is outside.  A mutant that touches gap rows only cannot show in the output (a
+    gap row is zero whatever the product was) and must be outside the bound of the product."""
+    p = build()
+    ref = sc.gemm_reference(p)
+    A, W, y, b = ref["Aim"], ref["Wim"], ref["pre"], ref["b_pre"]
+    emu = fb.split_emulation(A, W, ref["sa"], ref["sw"])
+    if p.get("bias") is not None:
+        emu = emu + p["bias"]
+    assert emu.dtype == np.float32 and fb.ratio(emu, y, b) <= 1.0
+    assert _through_epilogue(p, ref, emu.astype(np.float64)) <= 1.0
+    gap = np.zeros(p["M"], bool) if p.get("rowvalid") is None else p["rowvalid"] < 0
+    for mname, wrong in {**fb.mutants(A, W, y), **fb.split_mutants(A, W, y, slab=p["loud"])}.items():
+        assert fb.ratio(wrong, y, b) > 1.0, f"the product bound accepts the '{mname}' mutant"
+        if not gap[np.any(wrong != y, axis=1)].all():
+            assert _through_epilogue(p, ref, wrong) > 1.0, f"the output bound accepts the '{mname}' mutant"
+    if p.get("acc2"):           # (d) C2 overwritten where acc2 asks for +=
+        over = sc.gemm_epilogue_reference(p, y, b, acc2=0)["C2"]
+        assert fb.ratio(over, ref["C2"], ref["b_C2"]) > 1.0
+    if p.get("res") is not None and gap.any() and p.get("epi", 0) == 0:      # (c) a gap row keeps its residual
+        for mname, wrong in fb.gemm_epilogue_mutants(ref["C"], p["res"][:, :ref["C"].shape[1]], np.flatnonzero(gap)).items():
+            assert fb.ratio(wrong, ref["C"], ref["b_C"]) > 1.0, mname
+    if name == "skipped-tap":   # a kernel that ignored tap_w and took the weight rows of tap t for the t-th tap
+        q = dict(p, tap_w=[0, 1, 2, 3])
+        assert fb.ratio(sc.gemm_reference(q)["C"], ref["C"], ref["b_C"]) > 1.0
+
+
+def test_rowgemm_dropout_and_stop_head_bounds():
+    from oracle import philox_ref
+    M, K, N = 31, 64, 80
+    x, w, bias = sc.rowgemm_inputs(M, K, N, "drop")
+    pre, b = sc.matmul_reference(x, w, bias)
+    A, W = x.astype(np.float64), w.astype(np.float64)
+    _check_stage("dropout", A, W, pre, np.abs(A) @ np.abs(W), K, bias.astype(np.float64))
+    idx = np.arange(N, dtype=np.uint64)
+    keep, shifted = philox_ref.dropout_keep(idx, 0.25, 7), philox_ref.dropout_keep(idx + np.uint64(1), 0.25, 7)
+    want = np.where(keep, np.maximum(pre, 0) * (1 / 0.75), 0.0)
+    bound = fb.epilogue_step(np.maximum(pre, 0) / 0.75, b / 0.75)
+    y32 = np.where(keep, np.maximum(x @ w + bias, 0) * np.float32(1 / 0.75), np.float32(0))
+    assert y32.dtype == np.float32 and fb.ratio(y32, want, bound) <= 1.0
+    assert fb.ratio(np.where(shifted, np.maximum(pre, 0) / 0.75, 0.0), want, bound) > 1.0     # the mask of the next element
+    # the stop head: a dot product with one column; its bound must see a dropped product
+    for ln in (False, True):
+        x6, sw, g, beta = sc.stop_inputs(ln)
+        logit, b_logit, xn = sc.stop_reference(x6, sw, g, beta, 0.0)
+        s32 = (xn.astype(np.float32) @ sw)
+        assert fb.ratio(s32, logit, b_logit) <= 1.0
+        for mname, wrong in fb.mutants(xn, sw[:, None].astype(np.float64), logit[:, None]).items():
+            assert fb.ratio(wrong[:, 0], logit, b_logit) > 1.0, mname
+        assert np.all(np.abs(logit) > 100 * b_logit) and (logit > 0).sum() == 3
+
+
+def test_split_bound_floor_and_scales():
+    """act_scale / weight_scale restate blk_scale_exp / pk_weight_scale_exp: block maximum to [2^13, 2^14), clamps included"""
+    for v in (1.0, 0.7, 3e-9, 2.0 ** -41, 1e30, 0.0):
+        s = float(fb.act_scale(np.float32(v)))
+        if 2.0 ** -40 <= v < 2.0 ** 74:
+            assert 2.0 ** 13 <= v * s < 2.0 ** 14
+    assert float(fb.act_scale(np.float32(0.0))) == float(fb.act_scale(np.float32(2.0 ** -41))) == 2.0 ** 53
+    for v in (1.0, 0.3, 17.0):
+        assert 2.0 ** 13 <= v * float(fb.weight_scale(v)) < 2.0 ** 14
+    assert float(fb.weight_scale(0.0)) == 1.0 and float(fb.weight_scale(2.0 ** -60)) == 2.0 ** 40
+
+
 def test_sinusoid_bound_accepts_the_fp32_formula_and_rejects_a_shifted_table():
     for size, npos, start, omega in sc.SIN_CASES:
         want, bound = sc.sinusoid_reference(npos, size, omega, start)
@@ -157,4 +314,16 @@ def test_sweeps_cover_what_they_promise():
     assert {c.B * c.Cout for c in sc.CELL_CASES} == {1, 5, 8, 129}
     assert {(c.Cin, c.k, c.dil) for c in sc.CELL_CASES} == {(64, 3, 1), (80, 2, 7), (5, 9, 3), (128, 1, 1)}
     assert {128, 129} <= {c.total_frames for c in sc.MEL_CFGS}
+    g = sc.GEMM_CASES
+    for rp in sc.GEMM_RES_POS:
+        sel = [c for c in g if c.res_pos == rp]
+        assert {c.M for c in sel} == set(sc.GEMM_M) and {c.N for c in sel} == set(sc.GEMM_N), rp
+        assert {(c.Cin, c.taps) for c in sel} == {(k[0], k[1]) for k in sc.GEMM_KSHAPES}
+        assert {c.pad for c in sel if c.taps == 5} == {0, 2, 4} and {c.pad for c in sel if c.taps == 3} == {0, 1, 2}
+        assert {c.act for c in sel} == {0, 1, 2} and {c.affine for c in sel} == {False, True}
+    assert {(c.M, c.N) for c in g} >= set(itertools.product(sc.GEMM_M, sc.GEMM_N))
+    assert {(c.K, c.N) for c in sc.ROW_CASES} == set(itertools.product(sc.ROW_K, sc.ROW_N))
+    assert {c.M for c in sc.ROW_CASES} == set(sc.ROW_M)
+    assert {(c.taps, c.loud) for c in sc.GEMM_TAIL_CASES} == {(ns, sl) for ns in (4, 5, 6, 7) for sl in range(ns)}
+    assert {5, 6} <= {c.taps * c.Cin // 32 for c in g} and all(c.taps * c.Cin >= 128 for c in g)
     assert math.isclose(fb.U, np.finfo(np.float32).eps / 2)
