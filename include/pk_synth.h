@@ -412,6 +412,28 @@ int pk_ss_encode(pk_ss* h, const int64_t* text, const int64_t* tones, const int3
                  int32_t* out_frames);
 /* Phase 2 (:197-218): expand, + sinusoid_position_encoding, decoder -> packed (sum(frames), output_size). */
 int pk_ss_decode(pk_ss* h, float* mel_out, int32_t flags);
+/* SpeedySpeech.forward (:166-184): pk_ss_encode with the durations given by the caller.  The duration predictor still
+ * runs (forward returns pred_durations: pk_ss_pred_durations); the given durations stand where the head's would, and
+ * pk_ss_decode follows as after pk_ss_encode.  durations: HOST int64, packed like text, every value >= 0 (PK_EINVAL
+ * otherwise); a duration of 0 owns no frame (expansion.py:33).  frame_lens: HOST (B) or NULL.  NULL: utterance b decodes
+ * sum(d_b) frames, each utterance as if it were alone (forward at B = 1).  Otherwise it decodes frame_lens[b] >= sum(d_b)
+ * frames (smaller: PK_EINVAL); the frames past sum(d_b) are zero rows plus the positional encoding and take part in every
+ * convolution.  That is one row of the reference's batched forward, which has no masks: pass the padded ids (id 0 embeds
+ * to zero), tok_lens = T_max and frame_lens = max_b sum(d_b) to reproduce it.  out_frames (B) host: the decoder lengths;
+ * they are known on the host, so the call does not wait for the device. */
+int pk_ss_encode_given(pk_ss* h, const int64_t* text, const int64_t* tones, const int32_t* tok_lens,
+                       const int64_t* durations, const int32_t* frame_lens, int32_t B, int32_t* out_frames);
+/* Packed (sum tok_lens) log-durations the duration predictor gave in the last encode; PK_HOST_IO honoured. */
+int pk_ss_pred_durations(pk_ss* h, float* out, int32_t flags);
+/* The evaluator's text_mask (speedyspeech_updater.py:122-123): the next pk_ss_duration_loss sums over the first
+ * n_valid[b] <= tok_lens[b] tokens of utterance b.  HOST (B); NULL = all tokens, which every encode restores. */
+int pk_ss_set_valid_tokens(pk_ss* h, const int32_t* n_valid, int32_t B);
+/* sums_out (B) double: sum over the utterance's tokens of huber_loss(pred, log(max(d, 1)), delta = 1)
+ * (paddle.fluid.layers.huber_loss: r = label - input; 0.5 r^2 for |r| <= 1, |r| - 0.5 beyond) of the last
+ * pk_ss_encode_given (speedyspeech_updater.py:129-136).  After a plain pk_ss_encode: PK_ESTATE.  The tokens are those
+ * pk_ss_set_valid_tokens named SINCE the last encode; every encode resets them to all tokens, so set them after
+ * pk_ss_encode_given and before this call. */
+int pk_ss_duration_loss(pk_ss* h, double* sums_out, int32_t flags);
 /* Test taps of the last encode: 0 = encodings (T_b, H), 1 = log-durations (T_b), 2 = durations (T_b). */
 int pk_ss_debug_read(pk_ss* h, int32_t what, int32_t b, float* host_out, int64_t n_floats);
 void pk_ss_destroy(pk_ss* h);
@@ -740,6 +762,21 @@ int pk_stftd_run(pk_stftd* h, const float* x, const float* y, const int32_t* len
 int pk_stftd_magnitude(pk_stftd* h, int32_t r, const float* wav, const int32_t* lens, int32_t B, float* out,
                        int32_t flags);
 void pk_stftd_destroy(pk_stftd* h);
+
+/* ------------------------------------------------- masked L1 + SSIM of mel pairs */
+/* The two spectrogram terms of the SpeedySpeech evaluator (speedyspeech_updater.py:119-140) in one pass over both
+ * images, and parakeet/modules/ssim.py:21-61 (channel = 1) as a metric of its own.
+ * pred, target: packed rows (sum lens, W), W in [1, 1024].  lens: HOST (B) valid rows of each pair; padded_lens: HOST (B)
+ * >= lens, or NULL = lens: the rows of each pair's SSIM map.  Rows at or past lens[b] read as zero in both images
+ * (decoded * spec_mask, target * spec_mask); borders are zero-padded by window_size / 2 on all four sides.  The window is
+ * the reference's: gaussian of sigma 1.5, exp in double, rounded to fp32, divided by its fp32 sum; C1 = 1e-4, C2 = 9e-4.
+ * window_size must be odd and >= 1 (PK_EINVAL; an even window changes the map's size in the reference) and at most 33
+ * (PK_EUNSUPPORTED).
+ * sums_out (B, 2) double: sum |pred - target| over the lens[b] x W valid entries; sum of the SSIM map over its
+ * padded_lens[b] x W entries.  A pair's two sums are the same bits alone and in any batch.
+ * ssim_map_out: NULL, or packed (sum padded_lens, W): the map itself.  PK_HOST_IO honoured for all data pointers. */
+int pk_mel_loss_run(pk_ctx* ctx, const float* pred, const float* target, const int32_t* lens, const int32_t* padded_lens,
+                    int32_t B, int32_t W, int32_t window_size, double* sums_out, float* ssim_map_out, int32_t flags);
 
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).

@@ -23,6 +23,7 @@ PK_PWG_C_HAS_CONTEXT = 2
 PK_APPLY_NORMALIZER = 4
 PK_TTS_KEEP_ATT = 8
 PK_PWG_MATH_F32, PK_PWG_MATH_BF16X3, PK_PWG_MATH_F16X3 = 0, 1, 2
+PK_MEL_LOSS_ROWS = 16      # csrc/pk_mel_loss.h: map rows per tile of pk_mel_loss_run
 _EXC = {
     -1: ValueError,
     -2: AssertionError,
@@ -197,6 +198,10 @@ def _declare(lib):
         "pk_ss_set_math": (C.c_int, [vp, i32]),
         "pk_ss_finalize": (C.c_int, [vp]),
         "pk_ss_encode": (C.c_int, [vp, i64p, i64p, i32p, i32, i32p]),
+        "pk_ss_encode_given": (C.c_int, [vp, i64p, i64p, i32p, i64p, i32p, i32, i32p]),
+        "pk_ss_pred_durations": (C.c_int, [vp, f32p, i32]),
+        "pk_ss_set_valid_tokens": (C.c_int, [vp, i32p, i32]),
+        "pk_ss_duration_loss": (C.c_int, [vp, C.c_void_p, i32]),
         "pk_ss_decode": (C.c_int, [vp, f32p, i32]),
         "pk_ss_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_ss_destroy": (None, [vp]),
@@ -247,6 +252,7 @@ def _declare(lib):
         "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),
         "pk_stftd_magnitude": (C.c_int, [vp, i32, f32p, i32p, i32, f32p, i32]),
         "pk_stftd_destroy": (None, [vp]),
+        "pk_mel_loss_run": (C.c_int, [vp, f32p, f32p, i32p, i32p, i32, i32, i32, C.c_void_p, f32p, i32]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),

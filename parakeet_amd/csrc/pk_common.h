@@ -142,6 +142,9 @@ struct pk_ctx_scratch {
     pk_dbuf row_amax;    // pk_gemm_launch: max|A[r, :]| per row when the caller does not supply it
     pk_dbuf row_amax2;
     pk_dbuf attn_amax;   // run_attention: max|q|, |k|, |v| per (utterance, head)
+    pk_dbuf mel_tab;     // pk_mel_loss_run: the call's tables, the tiles' partial sums, the staging of a PK_HOST_IO call
+    pk_dbuf mel_part;
+    pk_dbuf mel_io;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

@@ -82,6 +82,9 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->row_amax.release();
         kv.second->row_amax2.release();
         kv.second->attn_amax.release();
+        kv.second->mel_tab.release();
+        kv.second->mel_part.release();
+        kv.second->mel_io.release();
         delete kv.second;
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

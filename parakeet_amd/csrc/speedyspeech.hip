@@ -40,7 +40,7 @@ __global__ __launch_bounds__(128) void k_ss_embed(const int* __restrict__ text, 
 }
 
 // duration head: Linear(H, 1) (:113), then round(exp(.)) with paddle.round = half away from zero (:191-192);
-// one wave per row.  dur (float, integer-valued) = 0 on gap rows.
+// one wave per row.  dur (float, integer-valued) = 0 on gap rows; dur == NULL (pk_ss_encode_given) keeps the caller's.
 __global__ __launch_bounds__(256) void k_ss_duration(const float* __restrict__ h, int H, const float* __restrict__ w,
                                                      float bias, const int* __restrict__ row_utt, int rows,
                                                      float* __restrict__ pred, float* __restrict__ dur) {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_ss_duration(const float* __restrict__ h
         const bool valid = row_utt[r] >= 0;
         const float p = s + bias;
         pred[r] = valid ? p : 0.f;
-        dur[r] = valid ? floorf(expf(p) + 0.5f) : 0.f;   // exp > 0: half away from zero == floor(x + 0.5)
+        if (dur) dur[r] = valid ? floorf(expf(p) + 0.5f) : 0.f;   // exp > 0: half away from zero == floor(x + 0.5); NULL: given
     }
 }
 
@@ -88,7 +88,9 @@ __global__ __launch_bounds__(256) void k_ss_cumsum(const float* __restrict__ dur
 }
 
 // expand (:194-209: frame f of an utterance copies the token whose duration interval contains f; tokens with
-// d < 1 own no frame) + sinusoid_position_encoding(t_dec, H) (:213-215), gap rows -> 0
+// d < 1 own no frame) + sinusoid_position_encoding(t_dec, H) (:213-215), gap rows -> 0.  A frame at or past the utterance's
+// last cumulative sum (pk_ss_encode_given with frame_lens: the rectangle of SpeedySpeech.forward, expansion.py:28-36) has no
+// source token: a zero row plus the positional encoding.  After pk_ss_encode every frame lies below that sum.
 __global__ __launch_bounds__(128) void k_ss_expand(const float* __restrict__ enc, const int* __restrict__ cum,
                                                    const int* __restrict__ tok_start, const int* __restrict__ tok_len,
                                                    const int* __restrict__ row_utt, const int* __restrict__ row_pos,
@@ -107,11 +109,54 @@ __global__ __launch_bounds__(128) void k_ss_expand(const float* __restrict__ enc
         else lo = mid + 1;
     }
     const float* src = enc + (long)(s0 + lo) * H;
+    const bool past = f >= cum[s0 + n - 1];
     for (int c = threadIdx.x; c < H; c += blockDim.x) {
         const float channel = (float)(c & ~1);
         const float p = (float)f / powf(10000.0f, channel / (float)H);
-        x[(long)r * H + c] = src[c] + ((c & 1) ? cosf(p) : sinf(p));
+        x[(long)r * H + c] = (past ? 0.f : src[c]) + ((c & 1) ? cosf(p) : sinf(p));
     }
+}
+
+// the log-durations of the row timeline (gap rows between the utterances) packed by utterance; one block per utterance, its
+// offset in the packed array is the sum of the lengths before it
+__global__ __launch_bounds__(256) void k_ss_pack_pred(const float* __restrict__ pred, const int* __restrict__ seg_start,
+                                                      const int* __restrict__ seg_len, float* __restrict__ out) {
+    __shared__ int sh[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int a = 0;
+    for (int i = t; i < b; i += 256) a += seg_len[i];
+    sh[t] = a;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (t < d) sh[t] += sh[t + d];
+        __syncthreads();
+    }
+    const int off = sh[0], s0 = seg_start[b], n = seg_len[b];
+    for (int i = t; i < n; i += 256) out[off + i] = pred[s0 + i];
+}
+
+// duration loss of the evaluator (speedyspeech_updater.py:129-136): huber_loss(pred, log(max(d, 1)), delta = 1) with
+// r = label - input, 0.5 r^2 for |r| <= 1, |r| - 0.5 beyond; summed over the first n_valid[b] tokens of utterance b.  One block
+// per utterance: thread t adds tokens t, t + 256, ... in ascending order in fp64, then a tree (as k_stftd_fold): the order
+// depends on the utterance alone.
+__global__ __launch_bounds__(256) void k_ss_duration_loss(const float* __restrict__ pred, const float* __restrict__ dur,
+                                                          const int* __restrict__ seg_start, const int* __restrict__ n_valid,
+                                                          double* __restrict__ out) {
+    __shared__ double sh[256];
+    const int b = blockIdx.x, t = threadIdx.x, s0 = seg_start[b], n = n_valid[b];
+    double a = 0.0;
+    for (int i = t; i < n; i += 256) {
+        const float r = logf(fmaxf(dur[s0 + i], 1.f)) - pred[s0 + i];
+        const float ar = fabsf(r);
+        a += (double)(ar <= 1.f ? 0.5f * r * r : ar - 0.5f);
+    }
+    sh[t] = a;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (t < d) sh[t] += sh[t + d];
+        __syncthreads();
+    }
+    if (t == 0) out[b] = sh[0];
 }
 
 struct Dense {
@@ -165,7 +210,7 @@ struct pk_ss {
     pk_ctx* ctx = nullptr;
     pk_ss_cfg cfg;
     pk_param_map params;
-    bool finalized = false, encoded = false;
+    bool finalized = false, encoded = false, given = false;   // given: the last encode took its durations from the caller
     int H = 0, gap = 1, lead = 8;
     int math = PK_GEMM_MATH_F16X3;
     std::vector<float> arena_h;
@@ -181,8 +226,8 @@ struct pk_ss {
     std::vector<float> h_out_scale, h_out_shift;
     // per call
     Timeline tl_tok, tl_frm;
-    pk_dbuf d_text, d_tone, d_e, d_a, d_b, d_c, d_enc, d_pred, d_dur, d_cum, d_frames, d_rowmap, d_stage;
-    std::vector<int> frames;
+    pk_dbuf d_text, d_tone, d_e, d_a, d_b, d_c, d_enc, d_pred, d_dur, d_cum, d_frames, d_rowmap, d_stage, d_nvalid;
+    std::vector<int> frames, n_valid;
 
     const float* W(size_t off) const { return arena.as<float>() + off; }
 };
@@ -464,19 +509,40 @@ extern "C" int pk_ss_finalize(pk_ss* h) {
     return PK_OK;
 }
 
-extern "C" int pk_ss_encode(pk_ss* h, const int64_t* text, const int64_t* tones, const int32_t* tok_lens, int32_t B,
-                            int32_t* out_frames) {
-    if (!h || !text || !tok_lens || !out_frames) PK_FAIL(PK_EINVAL, "pk_ss_encode: NULL argument");
-    if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_ss_encode: call pk_ss_finalize first");
-    if (B <= 0) PK_FAIL(PK_EINVAL, "pk_ss_encode: batch size must be positive");
+namespace {
+// pk_ss_encode (durations == NULL: they come from the duration head) and pk_ss_encode_given
+int ss_encode(pk_ss* h, const char* who, const int64_t* text, const int64_t* tones, const int32_t* tok_lens,
+              const int64_t* durations, const int32_t* frame_lens, int32_t B, int32_t* out_frames) {
+    if (!h->finalized) PK_FAIL(PK_ESTATE, "%s: call pk_ss_finalize first", who);
+    if (B <= 0) PK_FAIL(PK_EINVAL, "%s: batch size must be positive", who);
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     const pk_ss_cfg& c = h->cfg;
     const int H = h->H;
-    if (tones && c.tone_size <= 0) PK_FAIL(PK_ESTATE, "pk_ss_encode: the model has no tone embedding");
+    if (tones && c.tone_size <= 0) PK_FAIL(PK_ESTATE, "%s: the model has no tone embedding", who);
     for (int b = 0; b < B; ++b)
-        if (tok_lens[b] <= 0) PK_FAIL(PK_EINVAL, "pk_ss_encode: utterance %d has %d tokens", b, tok_lens[b]);
+        if (tok_lens[b] <= 0) PK_FAIL(PK_EINVAL, "%s: utterance %d has %d tokens", who, b, tok_lens[b]);
+    std::vector<int> given_frames;
+    if (durations) {   // everything is checked before any state changes
+        given_frames.resize(B);
+        long o = 0;
+        for (int b = 0; b < B; ++b) {
+            long sum = 0;
+            for (int t = 0; t < tok_lens[b]; ++t, ++o) {
+                if (durations[o] < 0) PK_FAIL(PK_EINVAL, "%s: utterance %d, token %d: duration %lld is negative", who, b, t, (long long)durations[o]);
+                sum += durations[o];
+                if (sum > (1 << 24)) PK_FAIL(PK_EINVAL, "%s: utterance %d: the durations sum to more than 2^24 frames", who, b);
+            }
+            if (frame_lens) {
+                if (frame_lens[b] < sum || frame_lens[b] > (1 << 24))
+                    PK_FAIL(PK_EINVAL, "%s: utterance %d: frame_lens %d, the durations sum to %ld", who, b, frame_lens[b], sum);
+                sum = frame_lens[b];
+            }
+            given_frames[b] = (int)sum;
+        }
+    }
     h->encoded = false;
+    h->given = false;
     PK_TRY(build_timeline(ctx, h->tl_tok, tok_lens, B, h->gap));
     Timeline& tl = h->tl_tok;
     {
@@ -485,16 +551,23 @@ extern "C" int pk_ss_encode(pk_ss* h, const int64_t* text, const int64_t* tones,
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < tok_lens[b]; ++t, ++o) {
                 if (text[o] < 0 || text[o] >= c.vocab_size)
-                    PK_FAIL(PK_EINVAL, "pk_ss_encode: token id %lld out of [0,%d)", (long long)text[o], c.vocab_size);
+                    PK_FAIL(PK_EINVAL, "%s: token id %lld out of [0,%d)", who, (long long)text[o], c.vocab_size);
                 tx[tl.seg_start[b] + t] = (int)text[o];
                 if (tones) {
                     if (tones[o] < 0 || tones[o] >= c.tone_size)
-                        PK_FAIL(PK_EINVAL, "pk_ss_encode: tone id %lld out of [0,%d)", (long long)tones[o], c.tone_size);
+                        PK_FAIL(PK_EINVAL, "%s: tone id %lld out of [0,%d)", who, (long long)tones[o], c.tone_size);
                     tn[tl.seg_start[b] + t] = (int)tones[o];
                 }
             }
         PK_TRY(pk_upload(ctx, h->d_text, tx.data(), tx.size() * sizeof(int)));
         if (tones) PK_TRY(pk_upload(ctx, h->d_tone, tn.data(), tn.size() * sizeof(int)));
+    }
+    if (durations) {   // the caller's durations stand where the head's would (speedyspeech.py:176-177); uploaded before any launch
+        std::vector<float> dur(tl.rows_alloc, 0.f);
+        long o = 0;
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < tok_lens[b]; ++t, ++o) dur[tl.seg_start[b] + t] = (float)durations[o];
+        PK_TRY(pk_upload(ctx, h->d_dur, dur.data(), dur.size() * sizeof(float)));
     }
     pk_dbuf* bufs[] = {&h->d_e, &h->d_a, &h->d_b, &h->d_c, &h->d_enc};
     for (pk_dbuf* b : bufs) PK_TRY(act_reserve(h, *b, tl.rows_alloc, H));
@@ -535,14 +608,93 @@ extern "C" int pk_ss_encode(pk_ss* h, const int64_t* text, const int64_t* tones,
     PK_TRY(h->d_cum.reserve((size_t)tl.rows_alloc * 4));
     PK_TRY(h->d_frames.reserve((size_t)B * 4));
     PK_LAUNCH(ctx, "ss_duration", k_ss_duration, dim3(pk_div_up(rows, 4)), dim3(256), 0, cur, H, h->W(h->dur_w),
-              h->dur_b, rv, rows, h->d_pred.as<float>(), h->d_dur.as<float>());
+              h->dur_b, rv, rows, h->d_pred.as<float>(), durations ? (float*)nullptr : h->d_dur.as<float>());
     PK_LAUNCH(ctx, "ss_cumsum", k_ss_cumsum, dim3(B), dim3(256), 0, h->d_dur.as<float>(), tl.d_seg_start(),
               tl.d_seg_len(), h->d_cum.as<int>(), h->d_frames.as<int>());
-    h->frames.resize(B);
-    PK_HIP(hipMemcpyAsync(h->frames.data(), h->d_frames.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PK_HIP(hipStreamSynchronize(ctx->stream));   // t_dec is data dependent (:194-196)
+    h->n_valid.assign(tok_lens, tok_lens + B);
+    if (durations) {
+        h->frames = given_frames;   // known on the host: no sync for the frame counts
+    } else {
+        h->frames.resize(B);
+        PK_HIP(hipMemcpyAsync(h->frames.data(), h->d_frames.p, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipStreamSynchronize(ctx->stream));   // t_dec is data dependent (:194-196)
+    }
     for (int b = 0; b < B; ++b) out_frames[b] = h->frames[b];
     h->encoded = true;
+    h->given = durations != nullptr;
+    return PK_OK;
+}
+}  // namespace
+
+extern "C" int pk_ss_encode(pk_ss* h, const int64_t* text, const int64_t* tones, const int32_t* tok_lens, int32_t B,
+                            int32_t* out_frames) {
+    if (!h || !text || !tok_lens || !out_frames) PK_FAIL(PK_EINVAL, "pk_ss_encode: NULL argument");
+    return ss_encode(h, "pk_ss_encode", text, tones, tok_lens, nullptr, nullptr, B, out_frames);
+}
+
+extern "C" int pk_ss_encode_given(pk_ss* h, const int64_t* text, const int64_t* tones, const int32_t* tok_lens,
+                                  const int64_t* durations, const int32_t* frame_lens, int32_t B, int32_t* out_frames) {
+    if (!h || !text || !tok_lens || !durations || !out_frames) PK_FAIL(PK_EINVAL, "pk_ss_encode_given: NULL argument");
+    return ss_encode(h, "pk_ss_encode_given", text, tones, tok_lens, durations, frame_lens, B, out_frames);
+}
+
+extern "C" int pk_ss_pred_durations(pk_ss* h, float* out, int32_t flags) {
+    if (!h || !out) PK_FAIL(PK_EINVAL, "pk_ss_pred_durations: NULL argument");
+    if (!h->encoded) PK_FAIL(PK_ESTATE, "pk_ss_pred_durations: no encode has run");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const Timeline& tl = h->tl_tok;
+    long total = 0;
+    for (int b = 0; b < tl.B; ++b) total += tl.seg_len[b];
+    float* d_out = out;
+    if (flags & PK_HOST_IO) {
+        PK_TRY(h->d_stage.reserve((size_t)total * 4));
+        d_out = h->d_stage.as<float>();
+    }
+    PK_LAUNCH(ctx, "ss_pack_pred", k_ss_pack_pred, dim3(tl.B), dim3(256), 0, h->d_pred.as<float>(), tl.d_seg_start(),
+              tl.d_seg_len(), d_out);
+    if (flags & PK_HOST_IO) {
+        PK_HIP(hipMemcpyAsync(out, d_out, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PK_OK;
+}
+
+extern "C" int pk_ss_set_valid_tokens(pk_ss* h, const int32_t* n_valid, int32_t B) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_ss_set_valid_tokens: handle is NULL");
+    if (!h->encoded) PK_FAIL(PK_ESTATE, "pk_ss_set_valid_tokens: no encode has run");
+    const Timeline& tl = h->tl_tok;
+    if (!n_valid) {
+        h->n_valid = tl.seg_len;
+        return PK_OK;
+    }
+    if (B != tl.B) PK_FAIL(PK_ESHAPE, "pk_ss_set_valid_tokens: %d counts, the last encode had %d utterances", B, tl.B);
+    for (int b = 0; b < B; ++b)
+        if (n_valid[b] < 0 || n_valid[b] > tl.seg_len[b])
+            PK_FAIL(PK_EINVAL, "pk_ss_set_valid_tokens: utterance %d: %d of %d tokens", b, n_valid[b], tl.seg_len[b]);
+    h->n_valid.assign(n_valid, n_valid + B);
+    return PK_OK;
+}
+
+extern "C" int pk_ss_duration_loss(pk_ss* h, double* sums_out, int32_t flags) {
+    if (!h || !sums_out) PK_FAIL(PK_EINVAL, "pk_ss_duration_loss: NULL argument");
+    if (!h->encoded || !h->given) PK_FAIL(PK_ESTATE, "pk_ss_duration_loss: the last encode was not pk_ss_encode_given: there are no target durations");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const Timeline& tl = h->tl_tok;
+    const int B = tl.B;
+    PK_TRY(pk_upload(ctx, h->d_nvalid, h->n_valid.data(), (size_t)B * sizeof(int)));
+    double* d_out = sums_out;
+    if (flags & PK_HOST_IO) {
+        PK_TRY(h->d_stage.reserve((size_t)B * sizeof(double)));
+        d_out = h->d_stage.as<double>();
+    }
+    PK_LAUNCH(ctx, "ss_duration_loss", k_ss_duration_loss, dim3(B), dim3(256), 0, h->d_pred.as<float>(), h->d_dur.as<float>(),
+              tl.d_seg_start(), h->d_nvalid.as<int>(), d_out);
+    if (flags & PK_HOST_IO) {
+        PK_HIP(hipMemcpyAsync(sums_out, d_out, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PK_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return PK_OK;
 }
 
@@ -632,7 +784,7 @@ extern "C" void pk_ss_destroy(pk_ss* h) {
     pk_device_guard _dg(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
     pk_dbuf* bufs[] = {&h->arena, &h->arena16, &h->d_text, &h->d_tone, &h->d_e, &h->d_a, &h->d_b, &h->d_c, &h->d_enc,
-                       &h->d_pred, &h->d_dur, &h->d_cum, &h->d_frames, &h->d_rowmap, &h->d_stage, &h->tl_tok.d_tab,
+                       &h->d_pred, &h->d_dur, &h->d_cum, &h->d_frames, &h->d_rowmap, &h->d_stage, &h->d_nvalid, &h->tl_tok.d_tab,
                        &h->tl_frm.d_tab};
     for (auto* b : bufs) b->release();
     delete h;
