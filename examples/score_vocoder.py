@@ -5,7 +5,13 @@ means of the two -- what the reference's evaluator reports as eval/spectral_conv
 eval/log_stft_magnitude_loss when it scores one utterance per batch.  A pair of unequal length is trimmed to the shorter one,
 and the line says so.
 
+With --discriminator-checkpoint (a snapshot_iter_*.pdz, which carries discriminator_params beside generator_params; needs
+--config for the discriminator's shape) every line gains four columns from the recipe's discriminator: the mean logit of the
+generated audio, eval/adversarial_loss and eval/fake_loss of it and eval/real_loss of the recording; their corpus means follow
+the two STFT lines.  Without it the output is what it always was.
+
     python examples/score_vocoder.py --gen-dir generated --ref-dir recordings [--config conf/default.yaml]
+                                     [--discriminator-checkpoint snapshot_iter_400000.pdz]
 """
 import argparse
 import os
@@ -25,18 +31,26 @@ def main():
     ap.add_argument("--config", default=None, help="Parallel WaveGAN yaml; its stft_loss_params are used (default: the "
                                                    "reference's 1024/120/600, 2048/240/1200, 512/50/240, hann)")
     ap.add_argument("--batch", type=int, default=16, help="pairs per call")
+    ap.add_argument("--discriminator-checkpoint", default=None,
+                    help="snapshot with discriminator_params: adds the discriminator's columns (needs --config)")
     a = ap.parse_args()
-    params = {}
+    params, disc = {}, None
     if a.config:
         import yaml
         with open(a.config) as f:
-            params = dict(yaml.safe_load(f).get("stft_loss_params") or {})
+            cfg = yaml.safe_load(f)
+        params = dict(cfg.get("stft_loss_params") or {})
+    if a.discriminator_checkpoint:
+        if not a.config:
+            raise SystemExit("--discriminator-checkpoint needs --config (the discriminator_params of the recipe)")
+        from parakeet_amd.checkpoint import load_pwg_discriminator
+        disc = load_pwg_discriminator(cfg, a.discriminator_checkpoint)
     crit = MultiResolutionSTFTLoss(**params)
     need = max(crit.fft_sizes) // 2 + 1
     ids = sorted(f[:-4] for f in os.listdir(a.gen_dir) if f.endswith(".wav") and os.path.exists(os.path.join(a.ref_dir, f)))
     if not ids:
         raise SystemExit("no <utt_id>.wav present in both directories")
-    rows = []
+    rows, drows = [], []
     for i in range(0, len(ids), a.batch):
         xs, ys, kept, notes = [], [], [], []
         for u in ids[i:i + a.batch]:
@@ -54,12 +68,21 @@ def main():
         if not kept:
             continue
         per = crit.per_utterance(xs, ys).mean(axis=1)            # (B, 2): mean over the resolutions
-        for u, x, (sc, mag), note in zip(kept, xs, per, notes):
-            print(f"{u}\t{len(x)}\t{sc:.6f}\t{mag:.6f}{note}")
+        extra = [""] * len(kept)
+        if disc is not None:
+            (sf, nf), (sr, nr), ml = disc.scores(xs), disc.scores(ys), disc.mean_logit(xs)
+            d = np.stack([ml, sf[:, 0] / nf, sf[:, 1] / nf, sr[:, 0] / nr], 1)   # mean logit, adversarial, fake, real
+            extra = ["".join(f"\t{v:.6f}" for v in row) for row in d]
+            drows.extend(d)
+        for u, x, (sc, mag), e, note in zip(kept, xs, per, extra, notes):
+            print(f"{u}\t{len(x)}\t{sc:.6f}\t{mag:.6f}{e}{note}")
             rows.append((sc, mag))
     if rows:
         sc, mag = np.mean(rows, axis=0)
         print(f"spectral_convergence_loss\t{sc:.6f}\nlog_stft_magnitude_loss\t{mag:.6f}\tover {len(rows)} utterances")
+    if drows:
+        ml, adv, fake, real = np.mean(drows, axis=0)
+        print(f"mean_logit\t{ml:.6f}\nadversarial_loss\t{adv:.6f}\nfake_loss\t{fake:.6f}\nreal_loss\t{real:.6f}")
 
 
 if __name__ == "__main__":

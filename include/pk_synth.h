@@ -763,6 +763,55 @@ int pk_stftd_magnitude(pk_stftd* h, int32_t r, const float* wav, const int32_t* 
                        int32_t flags);
 void pk_stftd_destroy(pk_stftd* h);
 
+/* ------------------------------------------- Parallel WaveGAN discriminator */
+/* parakeet/models/parallel_wavegan/parallel_wavegan.py PWGDiscriminator.forward :523-630 for ragged batches, and the sums the
+ * evaluator's MSE terms are formed of (parallel_wavegan_updater.py:192-223).  layers - 1 blocks of Conv1D(kernel_size,
+ * dilation d_i, zero padding (kernel_size - 1) / 2 * d_i) + LeakyReLU(negative_slope), d_0 = 1 and d_i = i for
+ * dilation_factor 1, else dilation_factor^i; then Conv1D(conv_channels -> 1, kernel_size), no activation.  Inference only.
+ * The whole stack is one kernel (csrc/pwg_disc.hip): a window of 256 samples (128 above 64 channels) of one utterance stays
+ * in LDS through all layers; its middle, window - 2 * halo samples, is the output tile.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): in_channels = out_channels = 1; kernel_size odd, 1 ... 9;
+ * layers 3 ... 16 (the reference cannot run 2); conv_channels a multiple of 16 in 16 ... 128; dilation_factor >= 1 with the
+ * receptive field per side, halo = (kernel_size - 1) / 2 * (sum of the d_i + 1), AT MOST 112 SAMPLES up to 64 channels and
+ * 48 above (the released recipes: 38). */
+typedef struct pk_pwgd pk_pwgd;
+typedef struct {
+    int32_t in_channels;      /* 1 */
+    int32_t out_channels;     /* 1 */
+    int32_t kernel_size;      /* 3 */
+    int32_t layers;           /* 10 */
+    int32_t conv_channels;    /* 64 */
+    int32_t dilation_factor;  /* 1 */
+    float negative_slope;     /* 0.2 */
+    int32_t bias;             /* 1 */
+} pk_pwgd_cfg;
+int pk_pwgd_create(pk_ctx* ctx, const pk_pwgd_cfg* cfg, pk_pwgd** out);
+/* name: the reference's state-dict key, "conv_layers.{2i}.weight" (or .weight_g / .weight_v, folded at finalize) and
+ * "conv_layers.{2i}.bias" for block i = 0 ... layers - 1 (the last one is the output conv). */
+int pk_pwgd_set_param(pk_pwgd* h, const char* name, const float* data, const int64_t* shape, int32_t ndim);
+int pk_pwgd_finalize(pk_pwgd* h);
+/* PK_PWG_MATH_F16X3 (default; the activations' block scale is measured per window and layer, the weights carry one exponent
+ * per tensor) or PK_PWG_MATH_F32.  Block 0 and the output conv are fp32 FMAs in both.  PK_PWG_MATH_BF16X3: PK_EUNSUPPORTED. */
+int pk_pwgd_set_math(pk_pwgd* h, int32_t mode);
+/* The kernel's output tile and the receptive field per side (samples).  Tiles start at utterance-relative multiples of tile. */
+int pk_pwgd_tile_samples(pk_pwgd* h, int32_t* tile, int32_t* halo);
+/* wav: packed samples of B utterances, lens (B, host) >= 1 each.
+ * logits_out: NULL, or packed (sum lens) logits.  With NULL no logit is written to memory.
+ * sums_out: NULL, or (B, 2) float64: [0] sum (p - 1)^2, [1] sum p^2 over the utterance's logits p (terms in fp32, a tile's
+ * terms added in fp32, an utterance's tiles in fp64 in a fixed order; no atomics).
+ * An utterance's logits and sums are bit-identical alone, in any batch and at any position in it.
+ * PK_EINVAL: NULL wav / lens, B <= 0, an empty utterance.  PK_ESTATE before pk_pwgd_finalize.
+ * flags: PK_HOST_IO if wav / logits_out / sums_out are host pointers (then synchronous). */
+int pk_pwgd_run(pk_pwgd* h, const float* wav, const int32_t* lens, int32_t B, float* logits_out, double* sums_out,
+                int32_t flags);
+/* on != 0: every pk_pwgd_run keeps a copy of its input for pk_pwgd_debug_read (off by default: it costs a copy). */
+int pk_pwgd_set_debug(pk_pwgd* h, int32_t on);
+/* Test tap: the activation after block `layer` (0 ... layers - 2, after its LeakyReLU) of utterance b of the last run, copied
+ * to HOST as (conv_channels, lens[b]) channel-major, n_floats = that many (else PK_ESHAPE).  Runs the stack again over that
+ * utterance in the handle's current math.  PK_ESTATE without a run under pk_pwgd_set_debug(h, 1). */
+int pk_pwgd_debug_read(pk_pwgd* h, int32_t layer, int32_t b, float* host_out, int64_t n_floats);
+void pk_pwgd_destroy(pk_pwgd* h);
+
 /* ------------------------------------------------- masked L1 + SSIM of mel pairs */
 /* The two spectrogram terms of the SpeedySpeech evaluator (speedyspeech_updater.py:119-140) in one pass over both
  * images, and parakeet/modules/ssim.py:21-61 (channel = 1) as a metric of its own.

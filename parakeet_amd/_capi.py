@@ -113,6 +113,11 @@ class StftdCfg(C.Structure):
     _fields_ = [("n_res", C.c_int32), ("power_floor", C.c_float), ("log_floor", C.c_float)]
 
 
+class PwgdCfg(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("in_channels", "out_channels", "kernel_size", "layers", "conv_channels",
+                                          "dilation_factor")] + [("negative_slope", C.c_float), ("bias", C.c_int32)])
+
+
 class OpGemmCfg(C.Structure):
     """pk_op_gemm_cfg"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "res", "a_amax", "a2_amax", "rowvalid", "out_rowmap", "C", "C2",
@@ -252,6 +257,15 @@ def _declare(lib):
         "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),
         "pk_stftd_magnitude": (C.c_int, [vp, i32, f32p, i32p, i32, f32p, i32]),
         "pk_stftd_destroy": (None, [vp]),
+        "pk_pwgd_create": (C.c_int, [vp, C.POINTER(PwgdCfg), C.POINTER(vp)]),
+        "pk_pwgd_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),
+        "pk_pwgd_finalize": (C.c_int, [vp]),
+        "pk_pwgd_set_math": (C.c_int, [vp, i32]),
+        "pk_pwgd_tile_samples": (C.c_int, [vp, i32p, i32p]),
+        "pk_pwgd_run": (C.c_int, [vp, f32p, i32p, i32, f32p, C.c_void_p, i32]),
+        "pk_pwgd_set_debug": (C.c_int, [vp, i32]),
+        "pk_pwgd_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
+        "pk_pwgd_destroy": (None, [vp]),
         "pk_mel_loss_run": (C.c_int, [vp, f32p, f32p, i32p, i32p, i32, i32, i32, C.c_void_p, f32p, i32]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),

@@ -227,6 +227,24 @@ def load_pwg(config, checkpoint, stats):
     return PWGInference(ZScore(mu, sigma), vocoder)
 
 
+def load_pwg_discriminator(config, checkpoint):
+    """The discriminator a Parallel WaveGAN snapshot carries beside its generator (``models['discriminator']`` of
+    examples/parallel_wavegan/baker/train.py, saved as ``discriminator_params``): returns ``PWGDiscriminator`` built from the
+    config's ``discriminator_params`` and loaded from the archive's.  Needs no device until it scores."""
+    from .parallel_wavegan import PWGDiscriminator
+    cfg = _config(config)
+    if "discriminator_params" not in cfg:
+        raise KeyError("the config has no discriminator_params section")
+    model = PWGDiscriminator(**cfg["discriminator_params"])
+    state = load_params(checkpoint, "discriminator_params")
+    if not state:
+        raise ValueError(f"{checkpoint}: discriminator_params is empty (a generator-only export)")
+    model.set_state_dict(state)
+    model.remove_weight_norm()
+    model.eval()
+    return model
+
+
 def load_speedyspeech(config, checkpoint, stats, phones_dict, tones_dict, same_padding_resets_dilation=True):
     """The acoustic-model half of examples/speedyspeech/baker/synthesize_e2e.py:46-83: returns
     ``(SpeedySpeechInference, phone_id_map, tone_id_map)``."""

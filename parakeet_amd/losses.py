@@ -1,6 +1,6 @@
 """``parakeet/modules/losses.py``'s ``weighted_mean`` (:60-77) and ``masked_l1_loss`` (:80-100) on the HIP engine, and the
 sums behind them and behind ``parakeet_amd.ssim`` (``pk_mel_loss_run``, csrc/mel_loss.hip: masked L1 and SSIM of mel pairs in
-one pass).  ``guided_attention_loss`` and ``masked_softmax_with_cross_entropy`` are not implemented.  Inference only: no
+one pass).  ``pwg_evaluate`` forms the seven numbers of the Parallel WaveGAN evaluator.  ``guided_attention_loss`` and ``masked_softmax_with_cross_entropy`` are not implemented.  Inference only: no
 gradients."""
 import ctypes as C
 
@@ -10,7 +10,7 @@ import torch
 from . import _capi
 from .runtime import Context, dptr, wrap
 
-__all__ = ["weighted_mean", "masked_l1_loss", "mel_loss_sums"]
+__all__ = ["weighted_mean", "masked_l1_loss", "mel_loss_sums", "pwg_evaluate", "pwg_evaluate_per_utterance"]
 
 
 def _t(x):
@@ -89,3 +89,47 @@ def masked_l1_loss(prediction, target, mask):
     pack = lambda x: torch.cat([x[b, :int(lens[b])] for b in range(B)])   # noqa: E731
     sums = mel_loss_sums(pack(p), pack(t), lens, window_size=1)
     return wrap(torch.tensor(sums[:, 0].sum() / (float(lens.sum()) * D), dtype=torch.float32, device=ctx.device))
+
+
+def _utterances(x):
+    """(N, 1, T) or (N, T) -> list of N 1-D signals"""
+    t = _t(x)
+    if t.dim() == 3:
+        t = t.reshape(-1, t.shape[2])
+    if t.dim() != 2:
+        raise AssertionError(f"expected (N, 1, T) or (N, T), got {tuple(t.shape)}")
+    return [t[n] for n in range(t.shape[0])]
+
+
+def _pwg_numbers(adv, real, fake, sc, mag, lambda_adv):
+    return {"eval/adversarial_loss": adv, "eval/spectral_convergence_loss": sc, "eval/log_stft_magnitude_loss": mag,
+            "eval/generator_loss": lambda_adv * adv + sc + mag, "eval/real_loss": real, "eval/fake_loss": fake,
+            "eval/discriminator_loss": real + fake}
+
+
+def pwg_evaluate(generator, discriminator, stft_criterion, wav, mel, noise, lambda_adv):
+    """``PWGEvaluator.evaluate_core`` (parallel_wavegan_updater.py:180-231) for one rectangle: ``wav`` (N, 1, T) ground truth,
+    ``mel`` (N, aux, T' + 2 ctx), ``noise`` (N, 1, T) in place of the ``paddle.randn`` drawn inside the call.  Returns the
+    seven ``eval/*`` numbers as Python floats.  ``generator(noise, mel)`` is ``PWGGenerator.forward``;
+    ``discriminator.scores`` gives the sums of (p - 1)^2 and p^2 per utterance, from which the three MSE terms are formed
+    here in float64 as means over all N x T logits; ``stft_criterion(wav_, wav)`` is ``MultiResolutionSTFTLoss``."""
+    wav_ = generator(noise, mel)
+    s_fake, n_fake = discriminator.scores(_utterances(wav_))
+    s_real, n_real = discriminator.scores(_utterances(wav))
+    adv = float(s_fake[:, 0].sum() / n_fake.sum())
+    fake = float(s_fake[:, 1].sum() / n_fake.sum())
+    real = float(s_real[:, 0].sum() / n_real.sum())
+    sc, mag = stft_criterion(wav_, wav)
+    return _pwg_numbers(adv, real, fake, float(sc), float(mag), float(lambda_adv))
+
+
+def pwg_evaluate_per_utterance(discriminator, stft_criterion, generated, real, lambda_adv):
+    """The same seven numbers for a ragged corpus: ``generated`` and ``real`` are lists of 1-D signals, pairwise of equal
+    length; every pair is scored as the evaluator would score a batch of one.  Returns ``{key: (B,) float64 numpy}``;
+    ``stft_criterion.per_utterance`` supplies the two STFT losses, averaged over its resolutions."""
+    generated, real = list(generated), list(real)
+    s_fake, n_fake = discriminator.scores(generated)
+    s_real, n_real = discriminator.scores(real)
+    per = np.asarray(stft_criterion.per_utterance(generated, real), np.float64).mean(axis=1)   # (B, R, 2) -> (B, 2)
+    return _pwg_numbers(s_fake[:, 0] / n_fake, s_real[:, 0] / n_real, s_fake[:, 1] / n_fake, per[:, 0], per[:, 1],
+                        float(lambda_adv))

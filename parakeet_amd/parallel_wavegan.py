@@ -1,4 +1,4 @@
-"""Parallel WaveGAN generator behind the reference's Python API.
+"""Parallel WaveGAN generator and discriminator behind the reference's Python API.
 
 Mirrors parakeet/models/parallel_wavegan/parallel_wavegan.py:
 ``PWGGenerator`` (constructor kwargs :369-388, ``set_state_dict``, ``eval``,
@@ -9,6 +9,9 @@ Shapes: the default (in/out 1, kernel 3, residual 64, gate 128, skip 64, aux 80)
 configuration inside the generic envelope runs the shape-generic kernels (csrc/pwg_gen.hip): in/out 1, odd
 kernel_size 1 ... 9, residual and skip channels multiples of 16 in 16 ... 256, gate channels 32 ... 512 with
 gate_channels / 2 a multiple of 16, aux channels 1 ... 512.  Anything else raises NotImplementedError.
+
+``PWGDiscriminator`` (:523-630) runs in csrc/pwg_disc.hip, the whole stack as one kernel; ``ResidualPWGDiscriminator`` is
+not implemented.
 
 Extensions over the reference (superset, not a break): ``inference`` takes an
 optional ``noise=`` (the reference draws ``paddle.randn`` inside the call, which
@@ -244,3 +247,183 @@ class PWGInference:
 
     def eval(self):
         return self
+
+
+class PWGDiscriminator:
+    """``PWGDiscriminator`` (parallel_wavegan.py:523-630), inference only: ``forward`` on the reference's rectangle, and for
+    ragged batches ``forward_batch`` (logits), ``scores`` (the sums behind the evaluator's MSE terms, no logit stored) and
+    ``mean_logit``.  The engine handle is created at the first call that computes, so a model can be built and loaded from
+    a checkpoint without a device.
+
+    Envelope (``pk_pwgd_create``): kernel_size odd 1 ... 9, layers 3 ... 16, conv_channels a multiple of 16 in 16 ... 128, a
+    receptive field per side of at most 112 samples (48 above 64 channels); anything else raises NotImplementedError."""
+
+    def __init__(self, in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1,
+                 nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, bias=True,
+                 use_weight_norm=True, device=None):
+        assert kernel_size % 2 == 1          # parallel_wavegan.py:567
+        assert dilation_factor > 0           # :568
+        if nonlinear_activation != "LeakyReLU":
+            raise NotImplementedError(f"PWGDiscriminator: nonlinear_activation {nonlinear_activation!r} is not implemented; "
+                                      "the kernel's epilogue is LeakyReLU")
+        if layers in (1, 2):
+            raise NotImplementedError(f"PWGDiscriminator(layers={layers}): the reference builds its last conv with "
+                                      "in_channels inputs (:590-595) and cannot run two layers; one layer has no hidden block")
+        if in_channels != 1 or out_channels != 1:
+            raise NotImplementedError("PWGDiscriminator: only in_channels = out_channels = 1 (a waveform in, one logit per "
+                                      "sample out) is implemented")
+        params = dict(nonlinear_activation_params or {})
+        unknown = set(params) - {"negative_slope"}
+        if unknown:
+            raise NotImplementedError(f"PWGDiscriminator: LeakyReLU parameters {sorted(unknown)} are not implemented")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.layers, self.conv_channels = kernel_size, layers, conv_channels
+        self.dilation_factor = dilation_factor
+        self.negative_slope = float(params.get("negative_slope", 0.01))   # nn.LeakyReLU's default
+        self.bias = bool(bias)
+        self.use_weight_norm = use_weight_norm
+        self.training = True
+        self._device = device
+        self._state = {}
+        self._math = "f16x3"
+        self._ctx = self._h = None
+        self._finalized = False
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._ctx.lib.pk_pwgd_destroy(h)
+            except Exception:
+                pass
+
+    @property
+    def dilations(self):
+        """Dilation of every conv: the ``layers - 1`` hidden blocks (:571-577), then the output conv's 1."""
+        f = self.dilation_factor
+        return [1 if i == 0 else (i if f == 1 else f ** i) for i in range(self.layers - 1)] + [1]
+
+    # -- nn.Layer look-alikes ------------------------------------------------
+    def set_state_dict(self, state_dict):
+        self._state.update({k: to_numpy_f32(v) for k, v in state_dict.items()})
+        self._finalized = False
+
+    def state_dict(self):
+        return dict(self._state)
+
+    def eval(self):
+        self.training = False
+        return self
+
+    def remove_weight_norm(self):
+        """Numerically neutral here: weight_g / weight_v pairs are folded at finalize."""
+        return None
+
+    def set_math(self, mode):
+        """'f16x3' (default: 3-term split-fp16 MFMA on block-scaled operands) or 'f32' (exact fp32 MFMA)."""
+        if mode not in ("f32", "f16x3"):
+            raise NotImplementedError(f"PWGDiscriminator.set_math({mode!r}): 'f32' and 'f16x3' are implemented")
+        self._math = mode
+        if self._h:
+            self._apply_math()
+
+    def _apply_math(self):
+        m = {"f32": _capi.PK_PWG_MATH_F32, "f16x3": _capi.PK_PWG_MATH_F16X3}[self._math]
+        _capi.check(self._ctx.lib.pk_pwgd_set_math(self._h, m))
+
+    def _engine(self):
+        """The finalized handle on the current stream's context."""
+        ctx = Context.get(self._device)
+        if self._h is None:
+            cfg = _capi.PwgdCfg(self.in_channels, self.out_channels, self.kernel_size, self.layers, self.conv_channels,
+                                self.dilation_factor, self.negative_slope, 1 if self.bias else 0)
+            h = C.c_void_p()
+            _capi.check(ctx.lib.pk_pwgd_create(ctx.handle, C.byref(cfg), C.byref(h)))
+            self._ctx, self._h = ctx, h
+            self._apply_math()
+        if not self._finalized:
+            set_params(ctx.lib.pk_pwgd_set_param, self._h, self._state)
+            _capi.check(ctx.lib.pk_pwgd_finalize(self._h))
+            self._finalized = True
+        return ctx
+
+    def tile_samples(self):
+        """(output tile, receptive field per side) of the kernel, in samples (``pk_pwgd_tile_samples``)."""
+        ctx = self._engine()
+        t, hl = C.c_int32(), C.c_int32()
+        _capi.check(ctx.lib.pk_pwgd_tile_samples(self._h, C.byref(t), C.byref(hl)))
+        return t.value, hl.value
+
+    # -- scoring ---------------------------------------------------------------
+    def _run(self, wavs, logits, sums):
+        ctx = self._engine()
+        wavs = list(wavs)
+        if len(wavs) == 0:
+            raise ValueError("no signals given")
+        sig = [ctx.to_device(w).reshape(-1) for w in wavs]
+        lens = np.array([s.numel() for s in sig], dtype=np.int32)
+        x = torch.cat(sig) if len(sig) > 1 else sig[0]
+        out = ctx.empty((int(lens.sum()),)) if logits else None
+        acc = ctx.empty((len(sig), 2), dtype=torch.float64) if sums else None
+        _capi.check(ctx.lib.pk_pwgd_run(self._h, dptr(x), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(sig),
+                                        None if out is None else dptr(out), None if acc is None else dptr(acc), 0))
+        return lens, out, acc
+
+    def forward(self, x):
+        """(N, 1, T) audio -> (N, 1, T) logits (:602-614): every row an utterance of length T."""
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        if t.dim() != 3 or t.shape[1] != 1:
+            raise AssertionError(f"expected (N, 1, T), got {tuple(t.shape)}")
+        N, _, T = t.shape
+        _, out, _ = self._run([t[n, 0] for n in range(N)], True, False)
+        return wrap(out.reshape(N, 1, T))
+
+    __call__ = forward
+
+    def forward_batch(self, wavs):
+        """List of 1-D signals of any lengths -> list of (T_b,) logit tensors, one engine call."""
+        lens, out, _ = self._run(wavs, True, False)
+        res, o = [], 0
+        for n in lens:
+            res.append(wrap(out[o:o + int(n)]))
+            o += int(n)
+        return res
+
+    def scores(self, wavs):
+        """List of 1-D signals -> ((B, 2) float64 numpy ``[sum (p - 1)^2, sum p^2]`` over each utterance's logits p,
+        (B,) counts).  No logit is written to memory."""
+        lens, _, acc = self._run(wavs, False, True)
+        return acc.cpu().numpy(), lens.astype(np.int64)
+
+    def mean_logit(self, wavs):
+        """(B,) float64: the mean logit of each utterance, the usual learned score of a vocoder output.  Formed from the
+        logits of ``forward_batch`` (summed in float64), not from the two sums of ``scores``: sum p = (sum p^2 -
+        sum (p - 1)^2 + n) / 2 would cancel."""
+        return np.array([float(p.as_subclass(torch.Tensor).to(torch.float64).mean()) for p in self.forward_batch(wavs)])
+
+    def debug_layers(self, wavs):
+        """Test tap: the activation after every hidden block, a list (per utterance) of lists (per block) of
+        (conv_channels, T_b) float32 numpy (``pk_pwgd_debug_read``; runs the stack once more per block)."""
+        ctx = self._engine()
+        _capi.check(ctx.lib.pk_pwgd_set_debug(self._h, 1))
+        try:
+            lens, _, _ = self._run(wavs, False, True)
+            res = []
+            for b, n in enumerate(lens):
+                per = []
+                for layer in range(self.layers - 1):
+                    out = np.empty((self.conv_channels, int(n)), dtype=np.float32)
+                    _capi.check(ctx.lib.pk_pwgd_debug_read(self._h, layer, b, _capi.fptr(out), out.size))
+                    per.append(out)
+                res.append(per)
+            return res
+        finally:
+            _capi.check(ctx.lib.pk_pwgd_set_debug(self._h, 0))
+
+
+class ResidualPWGDiscriminator:
+    """parallel_wavegan.py:633-763, the WaveNet-style discriminator: not implemented."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("ResidualPWGDiscriminator is not implemented: no released recipe selects it "
+                                  "(DESIGN.md section 8, out of scope); PWGDiscriminator is")

@@ -225,6 +225,52 @@ def pwg_state(cfg=None, seed=42, weight_norm=False):
     return st
 
 
+PWG_DISC_LJSPEECH = dict(   # discriminator_params of examples/parallel_wavegan/baker/conf/default.yaml
+    in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1,
+    nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, bias=True, use_weight_norm=True)
+
+
+def pwg_disc_state(cfg=None, seed=77, weight_norm=False, peaked=False):
+    """Seeded PWGDiscriminator state dict under the reference's keys ``conv_layers.{2i}.weight`` (or weight_g / weight_v).
+
+    ``peaked``: every row of a weight has two dominant entries (+-[0.3, 0.6]) among small ones (+-5e-4, all non-zero) and a
+    norm g in [0.9, 1.3].  A worst-case error bound is carried from layer to layer through |W|, which amplifies by a row's
+    1-norm where the signal grows by its 2-norm; for dense rows the ratio is sqrt(k C) per layer and the bound of a 10-layer
+    stack says nothing.  Peaked rows keep it near 1.5, so that the derived bounds of tests/pwg_disc_ref.py stay far below
+    the size of the logits."""
+    cfg = dict(PWG_DISC_LJSPEECH, **(cfg or {}))
+    rng = np.random.default_rng(seed)
+    st = {}
+    C, k, layers = cfg["conv_channels"], cfg["kernel_size"], cfg["layers"]
+    for i in range(layers):
+        cin = cfg["in_channels"] if i == 0 else C
+        cout = cfg["out_channels"] if i == layers - 1 else C
+        name = f"conv_layers.{2 * i}"
+        lim = 1.0 / math.sqrt(cin * k)
+        if peaked:
+            w = rng.uniform(-5e-4, 5e-4, size=(cout, cin * k))
+            for o in range(cout):
+                idx = rng.choice(cin * k, size=min(2, cin * k), replace=False)
+                w[o, idx] = rng.uniform(0.3, 0.6, size=len(idx)) * rng.choice([-1.0, 1.0], size=len(idx))
+            w = w.reshape(cout, cin, k).astype(np.float32)
+            g = rng.uniform(0.9, 1.3, size=(cout,)).astype(np.float32)
+            lim = 0.1
+        else:
+            w = rng.uniform(-lim, lim, size=(cout, cin, k)).astype(np.float32)
+            g = rng.uniform(0.5, 1.5, size=(cout,)).astype(np.float32)
+        if weight_norm:
+            st[name + ".weight_g"] = g
+            st[name + ".weight_v"] = w
+        elif peaked:
+            norm = np.sqrt((w.astype(np.float64).reshape(cout, -1) ** 2).sum(1))
+            st[name + ".weight"] = (w.astype(np.float64) * (g / norm)[:, None, None]).astype(np.float32)
+        else:
+            st[name + ".weight"] = w
+        if cfg["bias"]:
+            st[name + ".bias"] = rng.uniform(-lim, lim, size=(cout,)).astype(np.float32)
+    return st
+
+
 def phoneme_ids(n_tokens, idim=80, seed=10086):
     """ids in [1, idim-2]: never the pad id 0, never <eos> = idim-1
     (parakeet/models/fastspeech2/fastspeech2.py:126,143)."""
