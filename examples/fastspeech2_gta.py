@@ -9,7 +9,10 @@ waveform is made here).  ``--test-metadata`` is the ``metadata.jsonl`` its norma
 ``utt_id``, ``text`` (phone ids; or ``phones``, mapped through ``--phones-dict``), ``durations`` (frames per phone),
 ``pitch`` and ``energy`` (paths of the normalised token-averaged (T, 1) .npy files) and, for a multi-speaker model,
 ``spk_id``.  For each utterance the script writes ``<utt_id>_gta.npy`` (r * sum(durations), n_mels), in the normalised
-space, or de-normalised with ``--denormalize``.
+space, or de-normalised with ``--denormalize``.  With ``--score`` every line also needs ``feats`` (path of the normalised
+(L, n_mels) .npy mel) and the script prints the five numbers of FastSpeech2Evaluator.evaluate_core
+(fastspeech2_updater.py:123-163: l1_loss, duration_loss, pitch_loss, energy_loss, loss) per utterance, each utterance scored
+as a batch of one against its ``feats``, and their means over the corpus.
 """
 import argparse
 import json
@@ -19,6 +22,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+NAMES = ("l1_loss", "duration_loss", "pitch_loss", "energy_loss", "loss")
 
 
 def parse_args(argv=None):
@@ -37,6 +42,7 @@ def parse_args(argv=None):
     ap.add_argument("--verbose", type=int, default=1)
     ap.add_argument("--batch-size", type=int, default=32, help="utterances per teacher-forced pass")
     ap.add_argument("--denormalize", action="store_true", help="write log-mels (ZScore.inverse applied)")
+    ap.add_argument("--score", action="store_true", help="print the evaluator's five numbers per utterance and over the corpus")
     return ap.parse_args(argv)
 
 
@@ -63,7 +69,8 @@ def read_metadata(path, phone_id_map=None):
                 text = np.asarray([phone_id_map[p] for p in d["phones"]], dtype=np.int64)
             items.append(dict(utt_id=str(d["utt_id"]), text=text,
                               durations=np.asarray(d["durations"], dtype=np.int64).reshape(-1),
-                              pitch=resolve(d["pitch"]), energy=resolve(d["energy"]), spk_id=d.get("spk_id")))
+                              pitch=resolve(d["pitch"]), energy=resolve(d["energy"]), spk_id=d.get("spk_id"),
+                              feats=None if d.get("feats") is None else resolve(d["feats"])))
     return items
 
 
@@ -78,19 +85,30 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     order = sorted(range(len(items)), key=lambda i: len(items[i]["text"]))     # batches of similar length
     bs, done = max(1, args.batch_size), 0
+    totals = np.zeros(len(NAMES))
     for i0 in range(0, len(order), bs):
         chunk = [items[i] for i in order[i0:i0 + bs]]
         spk = None
         if args.speaker_dict is not None and all(it["spk_id"] is not None for it in chunk):
             spk = np.asarray([it["spk_id"] for it in chunk], dtype=np.int64)
-        mels = am.teacher_forced_batch([it["text"] for it in chunk], [it["durations"] for it in chunk],
-                                       [np.load(it["pitch"]) for it in chunk], [np.load(it["energy"]) for it in chunk],
-                                       spk_ids=spk, denormalize=args.denormalize)
+        texts, durs = [it["text"] for it in chunk], [it["durations"] for it in chunk]
+        pitch, energy = [np.load(it["pitch"]) for it in chunk], [np.load(it["energy"]) for it in chunk]
+        mels = am.teacher_forced_batch(texts, durs, pitch, energy, spk_ids=spk, denormalize=args.denormalize)
         for it, mel in zip(chunk, mels):
             np.save(os.path.join(args.output_dir, f"{it['utt_id']}_gta.npy"), mel.cpu().numpy())
+        if args.score:
+            for it in chunk:
+                if it["feats"] is None:
+                    raise ValueError(f"{it['utt_id']}: --score needs 'feats'")
+            scores = am.evaluate_per_utterance(texts, durs, pitch, energy, [np.load(it["feats"]) for it in chunk], spk_ids=spk)
+            for it, sc in zip(chunk, scores):
+                print(it["utt_id"], ", ".join(f"{k}: {sc[k]:.6f}" for k in NAMES))
+                totals += [sc[k] for k in NAMES]
         done += len(chunk)
         if args.verbose:
             print(f"{done}/{len(items)} utterances")
+    if args.score and items:
+        print("corpus mean", ", ".join(f"{k}: {v:.6f}" for k, v in zip(NAMES, totals / len(items))))
 
 
 if __name__ == "__main__":

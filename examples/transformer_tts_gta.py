@@ -9,7 +9,12 @@ ids) and ``speech`` (path of the normalised (L, n_mels) .npy)).  For each uttera
 ``<utt_id>_gta.npy`` ((L // r) * r, n_mels) in the normalised space (the space a vocoder fine-tuned on GTA mels reads
 after its own normalisation) and, with ``--save-attention``, ``<utt_id>_att.npy`` (dlayers, aheads, L // r, T + 1), the
 encoder-decoder attention weights.  Prenet dropout stays on as in the reference; ``--seed`` + the utterance's index
-selects the engine's dropout stream.
+selects the engine's dropout stream.  With ``--score`` the script prints the numbers of
+TransformerTTSEvaluator.evaluate_core (transformer_tts_updater.py:222-322: bce_loss, l1_loss, l2_loss, enc_dec_attn_loss,
+encoder_alpha, decoder_alpha, loss) per utterance, each utterance scored as a batch of one against its ``speech`` with the
+dropout stream of its GTA mel, and their means over the corpus; ``--loss-type``, ``--bce-pos-weight``,
+``--guided-attn-loss-sigma`` and ``--guided-attn-loss-lambda`` are the evaluator's options, ``--no-guided-attn-loss`` leaves
+the attention term out (a model with reduction_factor > 1 needs it).
 """
 import argparse
 import json
@@ -32,6 +37,12 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch-size", type=int, default=32, help="utterances per teacher-forced pass")
     ap.add_argument("--save-attention", action="store_true", help="also write <utt_id>_att.npy")
+    ap.add_argument("--score", action="store_true", help="print the evaluator's numbers per utterance and over the corpus")
+    ap.add_argument("--loss-type", default="L1", choices=("L1", "L2", "L1+L2"))
+    ap.add_argument("--bce-pos-weight", type=float, default=5.0)
+    ap.add_argument("--no-guided-attn-loss", action="store_true")
+    ap.add_argument("--guided-attn-loss-sigma", type=float, default=0.4)
+    ap.add_argument("--guided-attn-loss-lambda", type=float, default=1.0)
     return ap.parse_args(argv)
 
 
@@ -60,16 +71,28 @@ def main(argv=None):
     am = inf.acoustic_model
     items = read_metadata(args.test_metadata)
     os.makedirs(args.output_dir, exist_ok=True)
+    totals = {}
     for i0 in range(0, len(items), max(1, args.batch_size)):
         chunk = items[i0:i0 + max(1, args.batch_size)]
         speech = [np.load(p).astype(np.float32) for _, _, p in chunk]
-        outs = am.teacher_forced_batch([t for _, t, _ in chunk], speech, seeds=[args.seed + i0 + k for k in range(len(chunk))],
-                                       return_att=args.save_attention)
+        seeds = [args.seed + i0 + k for k in range(len(chunk))]
+        outs = am.teacher_forced_batch([t for _, t, _ in chunk], speech, seeds=seeds, return_att=args.save_attention)
         for (utt_id, _, _), (mel, att) in zip(chunk, outs):
             np.save(os.path.join(args.output_dir, f"{utt_id}_gta.npy"), mel.cpu().numpy())
             if att is not None:
                 np.save(os.path.join(args.output_dir, f"{utt_id}_att.npy"), att.cpu().numpy())
+        if args.score:
+            scores = am.evaluate_per_utterance([t for _, t, _ in chunk], speech, seeds=seeds, bce_pos_weight=args.bce_pos_weight,
+                                               loss_type=args.loss_type, use_guided_attn_loss=not args.no_guided_attn_loss,
+                                               guided_attn_loss_sigma=args.guided_attn_loss_sigma,
+                                               guided_attn_loss_lambda=args.guided_attn_loss_lambda)
+            for (utt_id, _, _), sc in zip(chunk, scores):
+                print(utt_id, ", ".join(f"{k}: {v:.6f}" for k, v in sc.items()))
+                for k, v in sc.items():
+                    totals[k] = totals.get(k, 0.0) + v
         print(f"{min(i0 + len(chunk), len(items))}/{len(items)} utterances")
+    if args.score and items:
+        print("corpus mean", ", ".join(f"{k}: {v / len(items):.6f}" for k, v in totals.items()))
 
 
 if __name__ == "__main__":

@@ -550,6 +550,12 @@ int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_lens, int32
  *             per decoder step, :623-636), utterances one after another, or NULL; needs PK_TTS_KEEP_ATT at infer
  * flags: PK_HOST_IO if the three are host pointers. */
 int pk_tts_read(pk_tts* h, float* mel_out, float* probs_out, float* att_out, int32_t flags);
+/* What the criterion needs of the last pk_tts_teacher beside pk_tts_read's outputs (TransformerTTSLoss, :801): before_out
+ * packed (sum frames, odim), the outputs before the postnet (:498), never de-normalised; logits_out packed (sum frames), the
+ * stop head BEFORE the sigmoid (:500) -- pk_tts_read's probabilities are sigmoid(these), and saturate where these do not.
+ * Either may be NULL.  Device pointers, or host pointers under PK_HOST_IO (then synchronous).  PK_ESTATE unless the handle's
+ * last completed call was pk_tts_teacher (the autoregressive decode keeps no logits). */
+int pk_tts_read_teacher(pk_tts* h, float* before_out, float* logits_out, int32_t flags);
 /* Test taps of the last infer: 0 = encoder output hs (T_b, adim), 1 = outs before the postnet (L_b, odim),
  * 2 = last decoder layer's output rows (L_b / reduction_factor, adim). */
 int pk_tts_debug_read(pk_tts* h, int32_t what, int32_t b, float* host_out, int64_t n_floats);
@@ -826,6 +832,43 @@ void pk_pwgd_destroy(pk_pwgd* h);
  * ssim_map_out: NULL, or packed (sum padded_lens, W): the map itself.  PK_HOST_IO honoured for all data pointers. */
 int pk_mel_loss_run(pk_ctx* ctx, const float* pred, const float* target, const int32_t* lens, const int32_t* padded_lens,
                     int32_t B, int32_t W, int32_t window_size, double* sums_out, float* ssim_map_out, int32_t flags);
+
+/* ------------------------------------- per-utterance sums of the acoustic models' criteria */
+/* seq_loss.hip: what FastSpeech2Loss, TransformerTTSLoss, GuidedAttentionLoss and Tacotron2Loss reduce, left as float64
+ * sums per utterance; the host forms the means (mask modes, weights, normalisations).  Common to the three calls: lengths
+ * and offsets are HOST arrays, offsets and strides count floats, PK_HOST_IO is honoured for all data pointers (then
+ * synchronous); every term enters a float64 accumulator at once and partial sums are combined in a fixed order (no
+ * atomics), so an utterance's sums are the same bits alone, in any batch, at any position and in either layout.
+ * PK_EINVAL: NULL argument, B <= 0, a negative length or offset.
+ *
+ * pk_pair_loss_run: pair b is rows[b] x W entries of pred and of target, W in [1, 8192] (above: PK_EUNSUPPORTED), row r at
+ * pred + pred_offs[b] + r * pred_stride (target likewise).  pred_offs / target_offs NULL: the pairs follow one another
+ * (packed; the stride must then be 0 or W).  A stride of 0 means W.  A padded (B, Lmax, W) rectangle is offs[b] =
+ * b * Lmax * W with stride W; a column block of a wider tensor is a larger stride.  rows[b] may be 0.
+ * sums_out (B, 2) double: sum |p - t| (difference in fp32), sum (p - t)^2 (the fp32 difference squared exactly). */
+int pk_pair_loss_run(pk_ctx* ctx, const float* pred, const float* target, const int64_t* pred_offs, const int64_t* target_offs,
+                     int64_t pred_stride, int64_t target_stride, const int32_t* rows, int32_t B, int32_t W, double* sums_out,
+                     int32_t flags);
+/* Paddle's binary_cross_entropy_with_logits term, (1 - y) x + (1 + (pos_weight - 1) y) (log1p(exp(-|x|)) + max(-x, 0)),
+ * evaluated in float64 in this form (finite for any finite logit) and summed over row b's lens[b] entries at
+ * logits + logit_offs[b], labels + label_offs[b] (NULL: packed).  labels are floats.  pos_weight must be finite and >= 0
+ * (PK_EINVAL); 1 is the unweighted loss.  sums_out (B) double. */
+int pk_bce_logits_run(pk_ctx* ctx, const float* logits, const float* labels, const int64_t* logit_offs,
+                      const int64_t* label_offs, const int32_t* lens, int32_t B, float pos_weight, double* sums_out,
+                      int32_t flags);
+/* Guided attention (Tachibana et al. 2017): utterance b owns maps[b] attention maps of rows[b] x cols[b] entries, map g's
+ * row s at att + offs[b] + g * map_stride + s * row_stride.  offs NULL: everything contiguous, utterance after utterance
+ * (both strides must be 0).  row_stride 0 means cols[b], map_stride 0 means rows[b] * row stride; a zero-padded
+ * (B, G, Smax, Tmax) tensor is offs[b] = b * G * Smax * Tmax, map_stride = Smax * Tmax, row_stride = Tmax.
+ * The guide W[s, t] = 1 - exp(-(t / cols[b] - s / rows[b])^2 / (2 sigma^2)) is formed in fp32 in the reference's order (two
+ * quotients, difference, square, division by fp32(2 sigma^2), expf) once per tile and never stored; it is
+ * GuidedAttentionLoss._make_guided_attention_mask (rows = olen, cols = ilen) and attention_guide (rows = dec_len, cols =
+ * enc_len) alike.  sums_out (B, 2) double: sum over g, s, t of W * A (product exact), sum of A.
+ * PK_EINVAL: sigma <= 0 or not finite, an utterance without a map, row or column, a stride below the extent it spans.
+ * PK_EUNSUPPORTED: more than 4096 maps in an utterance. */
+int pk_guided_attn_run(pk_ctx* ctx, const float* att, const int64_t* offs, int64_t map_stride, int64_t row_stride,
+                       const int32_t* maps, const int32_t* rows, const int32_t* cols, int32_t B, double sigma, double* sums_out,
+                       int32_t flags);
 
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).

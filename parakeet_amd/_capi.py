@@ -24,6 +24,9 @@ PK_APPLY_NORMALIZER = 4
 PK_TTS_KEEP_ATT = 8
 PK_PWG_MATH_F32, PK_PWG_MATH_BF16X3, PK_PWG_MATH_F16X3 = 0, 1, 2
 PK_MEL_LOSS_ROWS = 16      # csrc/pk_mel_loss.h: map rows per tile of pk_mel_loss_run
+# csrc/pk_seq_loss.h: entries per tile of pk_pair_loss_run / pk_bce_logits_run, rows x columns of pk_guided_attn_run's tile,
+# the longest fp32 accumulation chain of the three (0: float64 throughout)
+PK_SEQ_LOSS_PAIR_TILE, PK_SEQ_LOSS_GUIDE_ROWS, PK_SEQ_LOSS_GUIDE_COLS, PK_SEQ_LOSS_F32_CHAIN = 4096, 16, 64, 0
 _EXC = {
     -1: ValueError,
     -2: AssertionError,
@@ -223,6 +226,7 @@ def _declare(lib):
                                    i32p]),
         "pk_tts_teacher": (C.c_int, [vp, i64p, i32p, i32, f32p, i32p, C.POINTER(C.c_uint64), i32, i32p]),
         "pk_tts_read": (C.c_int, [vp, f32p, f32p, f32p, i32]),
+        "pk_tts_read_teacher": (C.c_int, [vp, f32p, f32p, i32]),
         "pk_tts_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_tts_destroy": (None, [vp]),
         "pk_taco_create": (C.c_int, [vp, C.POINTER(TacoCfg), C.POINTER(vp)]),
@@ -267,6 +271,9 @@ def _declare(lib):
         "pk_pwgd_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_pwgd_destroy": (None, [vp]),
         "pk_mel_loss_run": (C.c_int, [vp, f32p, f32p, i32p, i32p, i32, i32, i32, C.c_void_p, f32p, i32]),
+        "pk_pair_loss_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i64, i64, i32p, i32, i32, C.c_void_p, i32]),
+        "pk_bce_logits_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i32p, i32, C.c_float, C.c_void_p, i32]),
+        "pk_guided_attn_run": (C.c_int, [vp, f32p, i64p, i64, i64, i32p, i32p, i32p, i32, C.c_double, C.c_void_p, i32]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),

@@ -145,6 +145,9 @@ struct pk_ctx_scratch {
     pk_dbuf mel_tab;     // pk_mel_loss_run: the call's tables, the tiles' partial sums, the staging of a PK_HOST_IO call
     pk_dbuf mel_part;
     pk_dbuf mel_io;
+    pk_dbuf seq_tab;     // seq_loss.hip: the same three for pk_pair_loss_run, pk_bce_logits_run, pk_guided_attn_run
+    pk_dbuf seq_part;
+    pk_dbuf seq_io;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

@@ -85,6 +85,9 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->mel_tab.release();
         kv.second->mel_part.release();
         kv.second->mel_io.release();
+        kv.second->seq_tab.release();
+        kv.second->seq_part.release();
+        kv.second->seq_io.release();
         delete kv.second;
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

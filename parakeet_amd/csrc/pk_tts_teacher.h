@@ -44,6 +44,7 @@ int pk_tt_dropout(pk_ctx* ctx, float* x, int ld, int rows, int U, const int* row
 // timeline row (u, pos) -> row (pos + off) * B + u of a position-major array (pk_tts_read's layout of the AR decode)
 int pk_tt_scatter(pk_ctx* ctx, const float* src, int C, const int* row_utt, const int* row_pos, int rows, int B, int off,
                   float* dst);
-// prob_out + sigmoid per timeline row: probs[(pos * B + u) * r + k] = sigmoid(z[row] . w[:, k] + bias[k]) (w [A][r])
+// prob_out + sigmoid per timeline row: probs[(pos * B + u) * r + k] = sigmoid(z[row] . w[:, k] + bias[k]) (w [A][r]);
+// logits, in the same layout, keeps the sigmoid's argument
 int pk_tt_probs(pk_ctx* ctx, const float* z, int A, const float* w, const float* bias, int r, const int* row_utt,
-                const int* row_pos, int rows, int B, float* probs);
+                const int* row_pos, int rows, int B, float* probs, float* logits);

@@ -509,6 +509,7 @@ struct pk_tts : pk_fft_core {
     pk_tts_cfg cfg;
     pk_param_map params;
     bool finalized = false, inferred = false;
+    bool teacher = false;              // the last completed call was pk_tts_teacher (pk_tts_read_teacher serves it)
     int gapr = 1;
     bool dropout = true;
     bool kv_prefix = false;            // "kv_prefix" option (pk_tts_set_option), see pk_tts_infer
@@ -567,6 +568,7 @@ struct pk_tts : pk_fft_core {
     // pk_tts_teacher: the decoder on a timeline of its input rows
     Timeline tl_dec;
     pk_dbuf d_tsp, d_tspoff, d_tin, d_tp0, d_tp1, d_tpeb, d_tx, d_tn, d_tham, d_tqkv, d_tsq, d_tc, d_ta, d_tf, d_tout, d_tamax;
+    pk_dbuf d_tlogits;                 // the stop logits beside d_probs, same layout
 };
 
 // ---------------------------------------------------------------------------------------------- create / params
@@ -1119,6 +1121,7 @@ extern "C" int pk_tts_infer(pk_tts* h, const int64_t* ids, const int32_t* tok_le
     const int A = c.adim, H = c.aheads, dk = A / H, O = c.odim, J = c.dprenet_layers, U = J > 0 ? c.dprenet_units : 16;
     const int RF = c.reduction_factor, OR = O * RF;   // a decoder step emits RF frames: its Y row is [frame 0 | ... | frame RF-1]
     h->inferred = false;
+    h->teacher = false;
     h->B = B;
     h->keep_att = (flags & PK_TTS_KEEP_ATT) != 0;
     h->T.resize(B);
@@ -1709,6 +1712,7 @@ extern "C" int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_
         }
     }
     h->inferred = false;
+    h->teacher = false;
     h->B = B;
     h->keep_att = (flags & PK_TTS_KEEP_ATT) != 0;
     h->T.resize(B);
@@ -1748,6 +1752,7 @@ extern "C" int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_
     PK_TRY(rows_reserve(h->d_y, rowsPM, OR));
     PK_TRY(rows_reserve(h->d_xc_l[c.dlayers - 1], rowsPM, A));
     PK_TRY(h->d_probs.reserve((size_t)rowsPM * RF * sizeof(float)));
+    PK_TRY(h->d_tlogits.reserve((size_t)rowsPM * RF * sizeof(float)));
     const unsigned long long* d_seeds = nullptr;
     if (seeds) {
         PK_TRY(pk_upload(ctx, h->d_seeds, seeds, (size_t)B * sizeof(uint64_t)));
@@ -1874,11 +1879,13 @@ extern "C" int pk_tts_teacher(pk_tts* h, const int64_t* ids, const int32_t* tok_
     }
     PK_TRY(dense("tts_teacher_gemm_feat_out", h->feat_out, z, A, tout, OR, PK_ACT_NONE, nullptr, 0, !post && h3 ? ham : nullptr));
     PK_TRY(pk_tt_scatter(ctx, tout, OR, rutt, rpos, rows, B, 1, pk_fft_act_ptr(h->d_y, OR)));
-    PK_TRY(pk_tt_probs(ctx, z, A, h->W(h->prob_w), h->W(h->prob_bv), RF, rutt, rpos, rows, B, h->d_probs.as<float>()));
+    PK_TRY(pk_tt_probs(ctx, z, A, h->W(h->prob_w), h->W(h->prob_bv), RF, rutt, rpos, rows, B, h->d_probs.as<float>(),
+                       h->d_tlogits.as<float>()));
     h->steps = maxLin;
     h->frames.resize(B);
     for (int b = 0; b < B; ++b) out_frames[b] = h->frames[b] = Lin[b] * RF;
     h->inferred = true;
+    h->teacher = true;
     return PK_OK;
 }
 
@@ -1958,6 +1965,58 @@ extern "C" int pk_tts_read(pk_tts* h, float* mel_out, float* probs_out, float* a
     return PK_OK;
 }
 
+// before_outs (:498) and the stop logits (:500) of the last pk_tts_teacher, packed frame by frame like pk_tts_read's outputs:
+// the same gather out of the position-major step rows, without the postnet and without the sigmoid.
+extern "C" int pk_tts_read_teacher(pk_tts* h, float* before_out, float* logits_out, int32_t flags) {
+    if (!h || (!before_out && !logits_out)) PK_FAIL(PK_EINVAL, "pk_tts_read_teacher: NULL argument");
+    if (!h->inferred || !h->teacher) PK_FAIL(PK_ESTATE, "pk_tts_read_teacher: the last call must be a completed pk_tts_teacher");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const pk_tts_cfg& c = h->cfg;
+    const int B = h->B, O = c.odim, rf = c.reduction_factor;
+    long total = 0;
+    for (int b = 0; b < B; ++b) total += h->frames[b];
+    PK_TRY(pk_fft_build_timeline(ctx, h->tl_frm, h->frames.data(), B, h->gapr));
+    Timeline& tl = h->tl_frm;
+    {
+        std::vector<int> rowmap(tl.rows_alloc, -1);
+        int o = 0;
+        for (int b = 0; b < B; ++b)
+            for (int l = 0; l < h->frames[b]; ++l) rowmap[tl.seg_start[b] + l] = o++;
+        PK_TRY(pk_upload(ctx, h->d_rowmap, rowmap.data(), rowmap.size() * sizeof(int)));
+    }
+    const bool host = (flags & PK_HOST_IO) != 0;
+    auto gather = [&](const float* src, int C, int off, float* dst) -> int {
+        if (rf == 1)
+            PK_LAUNCH(ctx, "tts_gather", k_ar_gather, dim3(tl.rows), dim3(128), 0, src, C, B, off, tl.d_row_utt(), tl.d_row_pos(),
+                      h->d_rowmap.as<int>(), (const float*)nullptr, (const float*)nullptr, dst);
+        else
+            PK_LAUNCH(ctx, "tts_gather", k_tts_gather_r, dim3(tl.rows), dim3(128), 0, src, C, B, rf, off, tl.d_row_utt(),
+                      tl.d_row_pos(), h->d_rowmap.as<int>(), (const float*)nullptr, (const float*)nullptr, dst);
+        return PK_OK;
+    };
+    if (before_out && total > 0) {
+        float* d = before_out;
+        if (host) {
+            PK_TRY(h->d_stage.reserve((size_t)total * O * sizeof(float)));
+            d = h->d_stage.as<float>();
+        }
+        PK_TRY(gather(pk_fft_act_ptr(h->d_y, O * rf), O, 1, d));
+        if (host) PK_HIP(hipMemcpyAsync(before_out, d, (size_t)total * O * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (logits_out && total > 0) {
+        float* d = logits_out;
+        if (host) {
+            PK_TRY(h->d_stage2.reserve((size_t)total * sizeof(float)));
+            d = h->d_stage2.as<float>();
+        }
+        PK_TRY(gather(h->d_tlogits.as<float>(), 1, 0, d));
+        if (host) PK_HIP(hipMemcpyAsync(logits_out, d, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (host) PK_HIP(hipStreamSynchronize(ctx->stream));
+    return PK_OK;
+}
+
 /* what: 0 = encoder output hs (T_b, adim), 1 = outs before the postnet (L_b, odim), 2 = last decoder layer's output
  * rows (L_b, adim). */
 extern "C" int pk_tts_debug_read(pk_tts* h, int32_t what, int32_t b, float* host_out, int64_t n_floats) {
@@ -2016,7 +2075,7 @@ extern "C" void pk_tts_destroy(pk_tts* h) {
     for (auto& b : h->d_mkv_l) b.release();
     {
         pk_dbuf* bt[] = {&h->d_tsp, &h->d_tspoff, &h->d_tin, &h->d_tp0, &h->d_tp1, &h->d_tpeb, &h->d_tx, &h->d_tn, &h->d_tham,
-                         &h->d_tqkv, &h->d_tsq, &h->d_tc, &h->d_ta, &h->d_tf, &h->d_tout, &h->d_tamax};
+                         &h->d_tqkv, &h->d_tsq, &h->d_tc, &h->d_ta, &h->d_tf, &h->d_tout, &h->d_tamax, &h->d_tlogits};
         for (pk_dbuf* b : bt) b->release();
         h->tl_dec.release();
     }

@@ -358,7 +358,8 @@ __global__ __launch_bounds__(128) void k_tt_scatter(const float* __restrict__ sr
 // one wave per row
 __global__ __launch_bounds__(256) void k_tt_probs(const float* __restrict__ z, int A, const float* __restrict__ w,
                                                   const float* __restrict__ bias, int r, const int* __restrict__ row_utt,
-                                                  const int* __restrict__ row_pos, int rows, int B, float* __restrict__ probs) {
+                                                  const int* __restrict__ row_pos, int rows, int B, float* __restrict__ probs,
+                                                  float* __restrict__ logits) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= rows) return;
     const int u = row_utt[q];
@@ -368,7 +369,12 @@ __global__ __launch_bounds__(256) void k_tt_probs(const float* __restrict__ z, i
         for (int c = lane; c < A; c += 64) s = fmaf(z[(long)q * A + c], w[(long)c * r + k], s);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (lane == 0) probs[((long)row_pos[q] * B + u) * r + k] = 1.f / (1.f + expf(-(s + bias[k])));
+        if (lane == 0) {
+            const long o = ((long)row_pos[q] * B + u) * r + k;
+            const float lg = s + bias[k];
+            probs[o] = 1.f / (1.f + expf(-lg));
+            logits[o] = lg;   // what the stop criterion takes (a saturated probability does not give it back)
+        }
     }
 }
 }  // namespace
@@ -427,8 +433,8 @@ int pk_tt_scatter(pk_ctx* ctx, const float* src, int C, const int* row_utt, cons
 }
 
 int pk_tt_probs(pk_ctx* ctx, const float* z, int A, const float* w, const float* bias, int r, const int* row_utt,
-                const int* row_pos, int rows, int B, float* probs) {
+                const int* row_pos, int rows, int B, float* probs, float* logits) {
     PK_LAUNCH(ctx, "tts_teacher_probs", k_tt_probs, dim3(pk_div_up(rows, 4)), dim3(256), 0, z, A, w, bias, r, row_utt, row_pos,
-              rows, B, probs);
+              rows, B, probs, logits);
     return PK_OK;
 }

@@ -5,7 +5,9 @@ kwargs :52-118, ``set_state_dict``, ``eval``, ``inference`` :468-558) and
 ``FastSpeech2Inference`` (:662-671).  All arithmetic runs in libpk_synth.so
 (csrc/fs2.hip on the transformer machinery of csrc/fft.hip, csrc/gemm.hip).
 ``forward`` (:286-375) and ``inference(use_teacher_forcing=True)`` run ``_forward(..., ds, ps, es,
-is_inference=False)`` (:433-442) with given durations, pitch and energy; the losses are out of scope.
+is_inference=False)`` (:433-442) with given durations, pitch and energy.  ``FastSpeech2Loss`` (:674-812) and
+``DurationPredictorLoss`` (modules/fastspeech2_predictor/duration_predictor.py:140-184) reduce on the engine
+(``pk_pair_loss_run``); ``evaluate_batch`` is ``FastSpeech2Evaluator.evaluate_core``.  No gradients.
 
 Extensions over the reference: ``inference_batch`` runs a ragged batch in one engine call (the
 reference's ``inference`` is one utterance per call), ``teacher_forced_batch`` does the same with given
@@ -323,6 +325,44 @@ class FastSpeech2:
             ys = ys[:, :int(olens_out.max())]
         return wrap(before_outs), wrap(after_outs), wrap(d_outs), wrap(p_outs), wrap(e_outs), ys, olens_out
 
+    def evaluate_batch(self, text, text_lengths, speech, speech_lengths, durations, pitch, energy, spk_id=None, spembs=None,
+                       use_masking=False, use_weighted_masking=False):
+        """``FastSpeech2Evaluator.evaluate_core`` (fastspeech2_updater.py:123-163) on one padded batch: ``forward``, then
+        ``FastSpeech2Loss`` -> ``{"l1_loss", "duration_loss", "pitch_loss", "energy_loss", "loss"}`` as Python floats (the
+        means and their sum formed in float64).  The flags default to the evaluator's."""
+        crit = FastSpeech2Loss(use_masking=use_masking, use_weighted_masking=use_weighted_masking)
+        before_outs, after_outs, d_outs, p_outs, e_outs, ys, olens = self.forward(
+            text, text_lengths, speech, speech_lengths, durations, pitch, energy, spembs=spembs, spk_id=spk_id)
+        return _loss_dict(*crit.terms(after_outs, before_outs, d_outs, p_outs, e_outs, ys, durations, pitch, energy,
+                                      text_lengths, olens))
+
+    def evaluate_per_utterance(self, texts, durations, pitch, energy, target_mels, spk_ids=None, spembs=None, tone_ids=None):
+        """The evaluator's five numbers of every utterance scored as a batch of one (no padding: the three masking modes
+        coincide) -> list of dicts.  One ragged encode, decode and loss pass; an utterance's numbers are the same bits in any
+        batch.  ``target_mels[b]`` is (r * sum(durations[b]), odim)."""
+        from .losses import pair_loss_sums
+        ctx = Context.get(self._ctx.device)
+        frames = self.encode_batch(texts, 1.0, spk_ids, spembs, tone_ids, durations, pitch, energy)
+        tgts = [ctx.to_device(t) for t in target_mels]
+        if len(tgts) != len(frames):
+            raise ValueError(f"{len(frames)} utterances, {len(tgts)} target mels")
+        for b, t in enumerate(tgts):
+            if t.dim() != 2 or tuple(t.shape) != (int(frames[b]), self.odim) or frames[b] == 0:
+                raise ValueError(f"pair {b}: target mel {tuple(t.shape)}, the durations give {int(frames[b])} frames of "
+                                 f"{self.odim} bins (none cannot be averaged)")
+        after, before = self.decode_packed(False), self.before_packed()
+        ys = torch.cat(tgts)
+        l1 = pair_loss_sums(before, ys, frames)[:, 0] + pair_loss_sums(after, ys, frames)[:, 0]
+        d, p, e = (np.concatenate(v) for v in self.read_predictions())
+        tok = np.asarray(self._last_tok, np.int64)
+        cat = lambda vals, dt: np.concatenate([_host(v).reshape(-1) for v in vals]).astype(dt)   # noqa: E731
+        log_ds = DurationPredictorLoss().log_targets(cat(durations, np.int64))
+        dur = pair_loss_sums(d, log_ds, tok, width=1)[:, 1]
+        pit = pair_loss_sums(p, cat(pitch, np.float32), tok, width=1)[:, 1]
+        ene = pair_loss_sums(e, cat(energy, np.float32), tok, width=1)[:, 1]
+        n = frames.astype(np.float64) * self.odim
+        return [_loss_dict(l1[b] / n[b], dur[b] / tok[b], pit[b] / tok[b], ene[b] / tok[b]) for b in range(len(frames))]
+
     def inference(self, text, speech=None, durations=None, pitch=None, energy=None, alpha=1.0,
                   use_teacher_forcing=False, spembs=None, spk_id=None, tone_id=None, denormalize=False):
         """(T,) int64 -> (L, odim); fastspeech2.py:468-558.  ``use_teacher_forcing=True`` needs ``durations`` (T,), ``pitch``
@@ -351,6 +391,74 @@ class FastSpeech2:
         out = np.empty((n_rows, width), dtype=np.float32)
         _capi.check(self._ctx.lib.pk_fs2_debug_read(self._h, what, b, _capi.fptr(out), out.size))
         return out[:, 0] if width == 1 else out
+
+
+class DurationPredictorLoss:
+    """duration_predictor.py:140-184: MSE between the predictor's log-domain outputs and ``log(targets + offset)``.  The
+    targets' logarithm is taken in float32 as the reference takes it; the squared differences are summed by
+    ``pk_pair_loss_run`` and divided on the host.  ``reduction`` "mean" or "sum" give a 0-d float32 device tensor, "none" the
+    elementwise tensor (plain tensor arithmetic: nothing is reduced)."""
+
+    def __init__(self, offset=1.0, reduction="mean"):
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction {reduction!r}")
+        self.offset, self.reduction = offset, reduction
+
+    def log_targets(self, targets):
+        ctx = Context.get()
+        return torch.log(ctx.to_device(targets, dtype=torch.float32) + self.offset)
+
+    def forward(self, outputs, targets):
+        from .losses import pair_loss_sums, scalar
+        ctx = Context.get()
+        o, t = ctx.to_device(outputs), self.log_targets(targets)
+        if o.shape != t.shape:
+            raise ValueError(f"outputs {tuple(o.shape)} against targets {tuple(t.shape)}")
+        if self.reduction == "none":
+            return wrap((o - t) ** 2)
+        s = pair_loss_sums(o.reshape(-1), t.reshape(-1), [o.numel()], width=1)[0, 1]
+        return scalar(s / o.numel() if self.reduction == "mean" else s, ctx)
+
+    __call__ = forward
+
+
+class FastSpeech2Loss:
+    """fastspeech2.py:674-812 with the reference's eleven arguments -> ``(l1_loss, duration_loss, pitch_loss,
+    energy_loss)``, 0-d float32 device tensors.  ``use_masking``: means over the valid frames / tokens; neither flag: means
+    over the padded rectangles as given; ``use_weighted_masking``: every utterance's sum divided by L_b * B * odim (mel) or
+    T_b * B (token terms).  ``after_outs=None`` leaves the L1 term to ``before_outs`` (:759, :777).  The device leaves
+    float64 sums per utterance (``pk_pair_loss_run``, the predictors' terms at W = 1); the means are formed on the host."""
+
+    def __init__(self, use_masking=True, use_weighted_masking=False):
+        from .losses import masking_mode
+        self._mode = masking_mode(use_masking, use_weighted_masking)
+        self.use_masking, self.use_weighted_masking = use_masking, use_weighted_masking
+        self.duration_criterion = DurationPredictorLoss(reduction="none" if use_weighted_masking else "mean")
+
+    def terms(self, after_outs, before_outs, d_outs, p_outs, e_outs, ys, ds, ps, es, ilens, olens):
+        """The four numbers in float64."""
+        from .losses import masked_pair_means
+        ctx = Context.get()
+        flat = lambda x: ctx.to_device(x).reshape(x.shape[0], -1)   # noqa: E731  (B, Tmax, 1) -> (B, Tmax)
+        l1 = masked_pair_means(before_outs, ys, olens, self._mode)[0]
+        if after_outs is not None:
+            l1 += masked_pair_means(after_outs, ys, olens, self._mode)[0]
+        dur = masked_pair_means(flat(d_outs), self.duration_criterion.log_targets(flat(ds)), ilens, self._mode)[1]
+        pitch = masked_pair_means(flat(p_outs), flat(ps), ilens, self._mode)[1]
+        energy = masked_pair_means(flat(e_outs), flat(es), ilens, self._mode)[1]
+        return l1, dur, pitch, energy
+
+    def forward(self, after_outs, before_outs, d_outs, p_outs, e_outs, ys, ds, ps, es, ilens, olens):
+        from .losses import scalar
+        return tuple(scalar(v) for v in self.terms(after_outs, before_outs, d_outs, p_outs, e_outs, ys, ds, ps, es, ilens,
+                                                   olens))
+
+    __call__ = forward
+
+
+def _loss_dict(l1, dur, pitch, energy):
+    return {"l1_loss": float(l1), "duration_loss": float(dur), "pitch_loss": float(pitch), "energy_loss": float(energy),
+            "loss": float(l1 + dur + pitch + energy)}
 
 
 class FastSpeech2Inference:

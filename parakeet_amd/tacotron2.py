@@ -3,7 +3,8 @@
 Mirrors parakeet/models/tacotron2.py: ``Tacotron2`` (constructor kwargs :626-649, ``set_state_dict``, ``eval``,
 ``infer`` :781-840 -> dict of mel_output / mel_outputs_postnet / alignments [/ stop_logits], ``forward`` :691-778 with
 eval semantics: the teacher-forced pass that ground-truth-aligned mels, scoring and alignment extraction need).  All
-arithmetic runs in libpk_synth.so (csrc/taco2.hip).  The loss and training-time dropout are out of scope;
+arithmetic runs in libpk_synth.so (csrc/taco2.hip).  ``Tacotron2Loss`` (:886-982) reduces on the engine (csrc/seq_loss.hip),
+``evaluate_batch`` is ``forward`` followed by it; gradients and training-time dropout are out of scope;
 reduction_factor > 1 is refused (the reference's ``infer`` and ``forward`` cannot run it either: the postnet gets the
 (B, T, d_mels * r) decoder output, :822-826, :762).
 
@@ -220,6 +221,51 @@ class Tacotron2:
                 res["stop_logits"][b, :L] = o["stop_logits"]
         return {k: wrap(v) for k, v in res.items()}
 
+    def evaluate_batch(self, text_inputs, text_lens, mels, output_lens, tones=None, global_condition=None, seed=0,
+                       use_stop_token_loss=True, use_guided_attention_loss=False, sigma=0.2):
+        """``forward`` on one padded batch, then ``Tacotron2Loss`` with the given options -> its dict as Python floats
+        (``loss``, ``mel_loss``, ``post_mel_loss`` and, where selected, ``guided_attn_loss`` / ``stop_loss``).  The MSE terms
+        and the stop loss are means over the whole padded rectangle, as in the reference.  On a ragged batch the engine's
+        rows past output_lens[b] are zeros (see ``forward``), where the reference decodes the padding: its padded mel rows,
+        and its padded stop logits in particular, are not zero, so the rectangle means differ there; for B = 1 and for equal
+        lengths they are the reference's."""
+        if use_stop_token_loss and not self.use_stop_token:
+            raise ValueError("use_stop_token_loss needs a model built with use_stop_token=True")
+        out = self.forward(text_inputs, text_lens, mels, output_lens, tones=tones, global_condition=global_condition, seed=seed)
+        B, T_mel = out["mel_output"].shape[:2]
+        ol = np.full(B, T_mel, dtype=np.int64) if output_lens is None else _ids(output_lens).reshape(-1)
+        crit = Tacotron2Loss(use_stop_token_loss, use_guided_attention_loss, sigma)
+        return {k: float(v) for k, v in crit.terms(out["mel_output"], out["mel_outputs_postnet"], mels, out["alignments"],
+                                                   ol, _ids(text_lens).reshape(-1), out.get("stop_logits")).items()}
+
+    def evaluate_per_utterance(self, texts, mels, tones=None, seeds=None, global_condition=None, use_stop_token_loss=True,
+                               use_guided_attention_loss=False, sigma=0.2):
+        """The criterion's numbers of every utterance scored as a batch of one -> list of dicts of Python floats.  Built on
+        ``teacher_forced_batch`` (one ragged pass, no padding); the sums come from one call per term over the packed
+        outputs, so an utterance's numbers are the same bits in any batch."""
+        from .losses import bce_with_logits_sums, guided_attention_sums, pair_loss_sums
+        if use_stop_token_loss and not self.use_stop_token:
+            raise ValueError("use_stop_token_loss needs a model built with use_stop_token=True")
+        ctx = Context.get(self._ctx.device)
+        outs = self.teacher_forced_batch(texts, mels, tones=tones, seeds=seeds, global_condition=global_condition)
+        L, T = np.asarray(self._last_frames, np.int64), np.asarray(self._last_tok, np.int64)
+        cat = lambda key: torch.cat([o[key].as_subclass(torch.Tensor).reshape(-1) for o in outs])   # noqa: E731
+        ys = torch.cat([ctx.to_device(m).reshape(-1) for m in mels]).reshape(-1, self.d_mels)
+        n = L.astype(np.float64) * self.d_mels
+        res = {"mel_loss": pair_loss_sums(cat("mel_output").reshape(-1, self.d_mels), ys, L)[:, 1] / n,
+               "post_mel_loss": pair_loss_sums(cat("mel_outputs_postnet").reshape(-1, self.d_mels), ys, L)[:, 1] / n}
+        total = res["mel_loss"] + res["post_mel_loss"]
+        if use_guided_attention_loss:
+            res["guided_attn_loss"] = guided_attention_sums(cat("alignments"), L, T, sigma)[:, 0] / (L * T)
+            total = total + res["guided_attn_loss"]
+        if use_stop_token_loss:
+            labels = torch.zeros(int(L.sum()), device=ctx.device)
+            labels[torch.as_tensor(np.cumsum(L) - 1, device=ctx.device)] = 1.0
+            res["stop_loss"] = bce_with_logits_sums(cat("stop_logits"), labels, L) / L
+            total = total + res["stop_loss"]
+        res["loss"] = total
+        return [{k: float(v[b]) for k, v in res.items()} for b in range(len(outs))]
+
     def infer(self, text_inputs, max_decoder_steps=1000, tones=None, global_condition=None, seed=0):
         """text_inputs (1, T) [or (T,)] int64 -> {"mel_output": (1, L, C), "mel_outputs_postnet": (1, L, C),
         "alignments": (1, L, T), "stop_logits": (1, L) with a stop token}; tacotron2.py:781-840."""
@@ -243,3 +289,52 @@ class Tacotron2:
         out = np.empty((self._last_tok[b], self.d_encoder), dtype=np.float32)
         _capi.check(self._ctx.lib.pk_taco_debug_read(self._h, what, b, _capi.fptr(out), out.size))
         return out
+
+
+class Tacotron2Loss:
+    """tacotron2.py:886-982 -> the reference's dict of 0-d float32 device tensors: ``loss``, ``mel_loss``,
+    ``post_mel_loss`` and, where selected, ``guided_attn_loss`` (``guided_attention_loss`` of modules/losses.py under
+    ``sigma``) and ``stop_loss``.  The MSE terms are means over the whole rectangle given; the stop labels are
+    ``one_hot(slens - 1, T_dec)`` and the BCE a mean over all B * T_dec logits (:960-971).  The device leaves float64 sums
+    (``pk_pair_loss_run``, ``pk_bce_logits_run``, ``pk_guided_attn_run``); means and the total are formed on the host."""
+
+    def __init__(self, use_stop_token_loss=True, use_guided_attention_loss=False, sigma=0.2):
+        self.use_stop_token_loss = use_stop_token_loss
+        self.use_guided_attention_loss = use_guided_attention_loss
+        self.sigma = sigma
+
+    def terms(self, mel_outputs, mel_outputs_postnet, mel_targets, attention_weights=None, slens=None, plens=None,
+              stop_logits=None):
+        """The dict in float64."""
+        from .losses import _lengths, masked_bce_mean, masked_pair_means, padded_guided_sums
+        ctx = Context.get()
+        mel_loss = masked_pair_means(mel_outputs, mel_targets, None, "none")[1]
+        post = masked_pair_means(mel_outputs_postnet, mel_targets, None, "none")[1]
+        losses = {"loss": mel_loss + post, "mel_loss": mel_loss, "post_mel_loss": post}
+        if self.use_guided_attention_loss:
+            if attention_weights is None or slens is None or plens is None:
+                raise ValueError("the guided attention loss needs attention_weights, slens and plens")
+            dl, el = _lengths(slens), _lengths(plens)
+            sums = padded_guided_sums(attention_weights, dl, el, self.sigma)
+            losses["guided_attn_loss"] = float(np.mean(sums[:, 0] / (dl * el).astype(np.float64)))
+            losses["loss"] += losses["guided_attn_loss"]
+        if self.use_stop_token_loss:
+            if stop_logits is None or slens is None:
+                raise ValueError("the stop token loss needs stop_logits and slens")
+            x = ctx.to_device(stop_logits)
+            sl = torch.as_tensor(_lengths(slens), device=ctx.device)
+            if x.dim() != 2 or sl.numel() != x.shape[0] or int(sl.min()) < 1 or int(sl.max()) > x.shape[1]:
+                raise ValueError(f"stop_logits {tuple(x.shape)} with slens {sl.tolist()}")
+            labels = torch.zeros_like(x)
+            labels[torch.arange(x.shape[0], device=ctx.device), sl - 1] = 1.0
+            losses["stop_loss"] = masked_bce_mean(x, labels, None, "none")
+            losses["loss"] += losses["stop_loss"]
+        return losses
+
+    def forward(self, mel_outputs, mel_outputs_postnet, mel_targets, attention_weights=None, slens=None, plens=None,
+                stop_logits=None):
+        from .losses import scalar
+        return {k: scalar(v) for k, v in self.terms(mel_outputs, mel_outputs_postnet, mel_targets, attention_weights, slens,
+                                                    plens, stop_logits).items()}
+
+    __call__ = forward
