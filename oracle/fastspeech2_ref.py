@@ -50,9 +50,10 @@ def scaled_posenc(W, x):
     return x + W["alpha"] * pe.unsqueeze(0)
 
 
-def attention(W, x, mask, n_head):
+def attention(W, x, mask, n_head, attn_out=None):
     """MultiHeadedAttention.forward attention.py:133-156 with query=key=value=x.
-    mask: (B,1,T) bool non-pad mask or None."""
+    mask: (B,1,T) bool non-pad mask or None.  attn_out: a list that receives the attention weights (B, H, T, T) (the
+    reference keeps them in ``self.attn``, :128)."""
     B, T, D = x.shape
     dk = D // n_head
     q = linear(x, W["linear_q.weight"], W["linear_q.bias"]).reshape(B, T, n_head, dk).transpose(1, 2)
@@ -67,6 +68,8 @@ def attention(W, x, mask, n_head):
         attn = masked_fill(attn, m, 0.0)
     else:
         attn = torch.softmax(scores, dim=-1)
+    if attn_out is not None:
+        attn_out.append(attn)
     ctx = torch.matmul(attn, v).transpose(1, 2).reshape(B, T, D)
     return linear(ctx, W["linear_out.weight"], W["linear_out.bias"])
 
@@ -86,12 +89,12 @@ def conv_ffn(W, x):
     return linear(h, W["w_2.weight"], W["w_2.bias"])
 
 
-def encoder_layer(W, x, mask, n_head, normalize_before=True, concat_after=False):
+def encoder_layer(W, x, mask, n_head, normalize_before=True, concat_after=False, attn_out=None):
     """EncoderLayer.forward encoder_layer.py:64-115 (no cache, dropout off)."""
     residual = x
     if normalize_before:
         x = layer_norm(x, W["norm1.weight"], W["norm1.bias"])
-    att = attention(W.sub("self_attn."), x, mask, n_head)
+    att = attention(W.sub("self_attn."), x, mask, n_head, attn_out)
     if concat_after:                                                          # :103-106
         x = residual + linear(torch.cat([x, att], dim=-1), W["concat_linear.weight"], W["concat_linear.bias"])
     else:
@@ -107,10 +110,11 @@ def encoder_layer(W, x, mask, n_head, normalize_before=True, concat_after=False)
     return x
 
 
-def encoder(W, xs, mask, n_layers, n_head, embed_ids, normalize_before=True, concat_after=False):
+def encoder(W, xs, mask, n_layers, n_head, embed_ids, normalize_before=True, concat_after=False, attn_out=None):
     """Encoder.forward encoder.py:171-192.  embed_ids=True: input_layer is
     nn.Embedding(padding_idx=0) followed by ScaledPositionalEncoding (embed.0 /
-    embed.1); False: positional encoding only (embed.0) -- fastspeech2.py:250-266."""
+    embed.1); False: positional encoding only (embed.0) -- fastspeech2.py:250-266.  attn_out: a list that receives
+    every layer's attention weights, in layer order."""
     if embed_ids:
         table = W["embed.0.weight"].clone()
         table[0] = 0.0  # padding_idx=0 -> zero row [paddle-semantics]
@@ -119,7 +123,7 @@ def encoder(W, xs, mask, n_layers, n_head, embed_ids, normalize_before=True, con
     else:
         x = scaled_posenc(W.sub("embed.0."), xs)
     for i in range(n_layers):
-        x = encoder_layer(W.sub(f"encoders.{i}."), x, mask, n_head, normalize_before, concat_after)
+        x = encoder_layer(W.sub(f"encoders.{i}."), x, mask, n_head, normalize_before, concat_after, attn_out)
     if not normalize_before:                                                  # encoder.py:190-191
         return x
     return layer_norm(x, W["after_norm.weight"], W["after_norm.bias"])
@@ -203,18 +207,20 @@ def integrate_spk_embed(W, hs, spembs, integration_type):
 
 
 def inference(state, ids, cfg=None, alpha=1.0, dtype=torch.float32, return_parts=False, spk_id=None,
-              spembs=None, tone_id=None):
+              spembs=None, tone_id=None, return_attention=False):
     """FastSpeech2.inference fastspeech2.py:468-558 for one utterance.
     ids: (T,) int64 -> normalised mel (L, odim).  spk_id (int) / spembs (D,): speaker conditioning of
-    the multi-speaker recipes (:396-402; spembs wins when both are given)."""
+    the multi-speaker recipes (:396-402; spembs wins when both are given).  return_attention (with return_parts): the
+    parts also carry "attn_enc" / "attn_dec", one (heads, T, T) tensor of attention weights per layer."""
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
+    attn_enc, attn_dec = ([], []) if return_attention else (None, None)
     W = Weights(state, dtype)
     x = torch.as_tensor(np.asarray(ids)).to(torch.int64)
     ilens = [int(x.shape[0])]                       # :519-521
     xs = x.unsqueeze(0)                             # :522
     x_masks = make_non_pad_mask(ilens).unsqueeze(-2)  # _source_mask :618-641
     hs = encoder(W.sub("encoder."), xs, x_masks, cfg["elayers"], cfg["aheads"], True,
-                 cfg.get("encoder_normalize_before", True), cfg.get("encoder_concat_after", False))  # :393
+                 cfg.get("encoder_normalize_before", True), cfg.get("encoder_concat_after", False), attn_enc)  # :393
     if cfg.get("spk_embed_dim") is not None:        # :396-402
         emb = None
         if spembs is not None:
@@ -247,7 +253,7 @@ def inference(state, ids, cfg=None, alpha=1.0, dtype=torch.float32, return_parts
     hs2 = hs + e_embs + p_embs                      # :430
     hs_up = length_regulate(hs2, d_outs, alpha)     # :432
     zs = encoder(W.sub("decoder."), hs_up, None, cfg["dlayers"], cfg["aheads"], False,
-                 cfg.get("decoder_normalize_before", True), cfg.get("decoder_concat_after", False))  # :455 (h_masks=None)
+                 cfg.get("decoder_normalize_before", True), cfg.get("decoder_concat_after", False), attn_dec)  # :455 (h_masks=None)
     before = linear(zs, W["feat_out.weight"], W["feat_out.bias"])        # :457
     odim = before.shape[-1] // cfg.get("reduction_factor", 1)
     before = before.reshape(before.shape[0], -1, odim)                   # (B, L * r, odim)
@@ -256,8 +262,12 @@ def inference(state, ids, cfg=None, alpha=1.0, dtype=torch.float32, return_parts
         after = before + postnet(W.sub("postnet."), before.transpose(1, 2),
                                  cfg["postnet_layers"]).transpose(1, 2)  # :463-464
     if return_parts:
-        return after[0], dict(hs=hs[0], p=p_outs[0, :, 0], e=e_outs[0, :, 0], d=d_outs[0],
-                              hs_up=hs_up[0], zs=zs[0], before=before[0])
+        parts = dict(hs=hs[0], p=p_outs[0, :, 0], e=e_outs[0, :, 0], d=d_outs[0],
+                     hs_up=hs_up[0], zs=zs[0], before=before[0])
+        if return_attention:
+            parts["attn_enc"] = [a[0] for a in attn_enc]
+            parts["attn_dec"] = [a[0] for a in attn_dec]
+        return after[0], parts
     return after[0]
 
 

@@ -87,11 +87,19 @@ def make_non_pad_mask(lengths):
 
 def sinusoid_table(length, d_model, dtype):
     """PositionalEncoding.extend_pe, fastspeech2_transformer/embedding.py:46-62.
-    The table is built in float32 (as the reference does) and then cast."""
+    Angles, sines and cosines are taken in float32 as the reference takes them, and the table is then cast; the frequencies
+    are float32 values too, but correctly rounded ones.
+
+    div_term is the float32 argument's exponential ROUNDED ONCE (taken in float64): a float32 ``exp`` is only good to its
+    last bit, which one differs between vector maths libraries and so between machines, and the angle position * div_term
+    multiplies that bit by the position -- 1.5e-5 in sin / cos at position 256, an input difference several times the
+    float32 rounding of a whole FFT stack (tests/fft_stack_cases.py).  Both users share it: the FastSpeech2 and the
+    TransformerTTS oracle (and the table of tests/test_ar_golden_cpu.py).  The engine's table (k_build_pe: libm's expf on the
+    host, correctly rounded for the widths in use) has the same frequencies bit for bit."""
     pe = torch.zeros(length, d_model, dtype=torch.float32)
     position = torch.arange(0, length, dtype=torch.float32).unsqueeze(1)
-    div_term = torch.exp(
-        torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
+    arg = torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model)
+    div_term = torch.exp(arg.to(torch.float64)).to(torch.float32)
     pe[:, 0::2] = torch.sin(position * div_term)
     pe[:, 1::2] = torch.cos(position * div_term)
     return pe.to(dtype)

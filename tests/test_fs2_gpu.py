@@ -206,7 +206,7 @@ def test_fs2_batch_composition_invariance():
         assert torch.equal(ref[b], rev[len(texts) - 1 - b].as_subclass(torch.Tensor)), b
     solo = model.inference_batch([texts[2]])[0].as_subclass(torch.Tensor)
     assert torch.equal(ref[2], solo)
-    for variant in (88, 44):
+    for variant in (88, 84, 48, 44):
         model.set_option("ffnp_variant", variant)
         out = model.inference_batch(texts)
         for b in range(len(texts)):
