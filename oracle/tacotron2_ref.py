@@ -57,8 +57,9 @@ def conv_bn_nlc(W, x):
     return y.transpose(1, 2)
 
 
-def encoder(W, x, n_conv):
-    """Tacotron2Encoder.forward :216-241, input_lens=None.  x (1, T, d_encoder)."""
+def encoder(W, x, n_conv, gate_hook=None):
+    """Tacotron2Encoder.forward :216-241, input_lens=None.  x (1, T, d_encoder).  ``gate_hook`` (tests only: a planted
+    defect) maps (input term, recurrent term) of the LSTM's gates, each (1, 4 Hh), to the gates."""
     for i in range(n_conv):
         x = torch.relu(conv_bn_nlc(W.sub(f"conv_batchnorms.{i}."), x))
     T = x.shape[1]
@@ -70,20 +71,34 @@ def encoder(W, x, n_conv):
         c = torch.zeros(1, Hh, dtype=x.dtype)
         seq = [None] * T
         for t in order:
-            h, c = lstm_cell(C, x[:, t], h, c)
+            if gate_hook is None:
+                h, c = lstm_cell(C, x[:, t], h, c)
+            else:
+                gates = gate_hook(linear(x[:, t], C["weight_ih"].t(), C["bias_ih"]), linear(h, C["weight_hh"].t(), C["bias_hh"]))
+                i, f, g, o = torch.chunk(gates, 4, dim=-1)
+                c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+                h = torch.sigmoid(o) * torch.tanh(c)
             seq[t] = h
         outs.append(torch.stack(seq, dim=1))
     return torch.cat(outs, dim=-1)
 
 
-def location_sensitive_attention(W, query, processed_key, value, attw_cat):
+def location_sensitive_attention(W, query, processed_key, value, attw_cat, hook=None):
     """LocationSensitiveAttention.forward attention.py:300-348, mask None.
-    query (1, d_query); processed_key (1, T, d_att); value (1, T, d_key); attw_cat (1, T, 2)."""
+    query (1, d_query); processed_key (1, T, d_att); value (1, T, d_key); attw_cat (1, T, 2).  ``hook`` (tests only: a
+    planted defect): ``hook("window", x, pad)`` returns the padded (1, 2, T + 2 pad) input of the location conv in place of
+    zero padding, ``hook("energy", e)`` the energies (1, T, 1) the softmax sees."""
     pq = linear(query.unsqueeze(1), W["query_layer.weight"])
     w = W["location_conv.weight"]
-    loc = conv1d(attw_cat.transpose(1, 2), w, None, padding=int((w.shape[-1] - 1) / 2)).transpose(1, 2)
+    pad = int((w.shape[-1] - 1) / 2)
+    if hook is None:
+        loc = conv1d(attw_cat.transpose(1, 2), w, None, padding=pad).transpose(1, 2)
+    else:
+        loc = conv1d(hook("window", attw_cat.transpose(1, 2), pad), w, None, padding=0).transpose(1, 2)
     ploc = linear(loc, W["location_layer.weight"])
     alignment = linear(torch.tanh(ploc + processed_key + pq), W["value.weight"])      # (1, T, 1)
+    if hook is not None:
+        alignment = hook("energy", alignment)
     weights = torch.softmax(alignment, dim=1)
     context = torch.matmul(weights.transpose(1, 2), value)                            # (1, 1, d_key)
     return context.squeeze(1), weights.squeeze(-1)
@@ -97,9 +112,12 @@ def postnet(W, x, n_layers):
 
 
 def infer(state, ids, cfg=None, tones=None, max_decoder_steps=1000, seed=0, drop="stream", dtype=torch.float32,
-          return_parts=False, global_condition=None):
+          return_parts=False, global_condition=None, hooks=None):
     """Tacotron2.infer :781-840 for one utterance.  ids (T,) int64.  Returns a dict with mel_output (L, d_mels),
-    mel_outputs_postnet (L, d_mels), alignments (L, T) and, with a stop token, stop_logits (L,)."""
+    mel_outputs_postnet (L, d_mels), alignments (L, T) and, with a stop token, stop_logits (L,).  ``hooks`` (tests only:
+    planted defects): a dict with "lsa" (``location_sensitive_attention``'s hook), "gates" (``encoder``'s) and
+    "no_cumulation" (the cumulative alignment stays zero)."""
+    hooks = hooks or {}
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
     if cfg.get("reduction_factor", 1) != 1:
         raise NotImplementedError("reduction_factor != 1: Tacotron2.infer cannot run it (postnet on (B, T, C * r), :822-826)")
@@ -110,7 +128,7 @@ def infer(state, ids, cfg=None, tones=None, max_decoder_steps=1000, seed=0, drop
         tn = torch.as_tensor(np.asarray(tones)).to(torch.int64).reshape(1, -1)
         te = W["embedding_tones.weight"][tn]
         emb = emb + torch.where((tn == 0).unsqueeze(-1), torch.zeros_like(te), te)    # padding_idx=0 [paddle-semantics]
-    key = encoder(W.sub("encoder."), emb, cfg["encoder_conv_layers"])                 # :811
+    key = encoder(W.sub("encoder."), emb, cfg["encoder_conv_layers"], hooks.get("gates"))   # :811
     enc_out = key
     if global_condition is not None:                                                  # :816-821
         g = torch.as_tensor(np.asarray(global_condition)).to(dtype).reshape(1, 1, -1)
@@ -138,8 +156,9 @@ def infer(state, ids, cfg=None, tones=None, max_decoder_steps=1000, seed=0, drop
                 keep = torch.as_tensor(drop(i, j, q.shape[1]))
                 q = torch.where(keep.unsqueeze(0), q / (1.0 - p), torch.zeros_like(q))
         att_h, att_c = lstm_cell(D.sub("attention_rnn."), torch.cat([q, ctx], dim=-1), att_h, att_c)   # :381-385
-        ctx, attw = location_sensitive_attention(A, att_h, pkey, key, torch.stack([attw, attw_cum], dim=-1))
-        attw_cum = attw_cum + attw                                                    # :397
+        ctx, attw = location_sensitive_attention(A, att_h, pkey, key, torch.stack([attw, attw_cum], dim=-1), hooks.get("lsa"))
+        if not hooks.get("no_cumulation"):
+            attw_cum = attw_cum + attw                                                # :397
         dec_h, dec_c = lstm_cell(D.sub("decoder_rnn."), torch.cat([att_h, ctx], dim=-1), dec_h, dec_c)   # :400-403
         hc = torch.cat([dec_h, ctx], dim=-1)
         mel = linear(hc, D["linear_projection.weight"], D["linear_projection.bias"])  # :411-413

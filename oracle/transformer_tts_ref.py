@@ -61,15 +61,18 @@ def stream_dropout(seed, n_layers, units, p=PRENET_DROPOUT_P):
     return drop
 
 
-def mha(W, q_in, kv_in, n_head):
+def mha(W, q_in, kv_in, n_head, hook=None):
     """MultiHeadedAttention.forward attention.py:133-156, mask None (or all ones).  q_in (B,Tq,D), kv_in (B,Tk,D).
-    Returns (output, attention weights (B, H, Tq, Tk))."""
+    Returns (output, attention weights (B, H, Tq, Tk)).  ``hook`` (tests only: a planted defect) maps the per-head
+    (q, k, v), each (B, H, T, dk), to the three the attention is computed from."""
     B, Tq, D = q_in.shape
     Tk = kv_in.shape[1]
     dk = D // n_head
     q = linear(q_in, W["linear_q.weight"], W["linear_q.bias"]).reshape(B, Tq, n_head, dk).transpose(1, 2)
     k = linear(kv_in, W["linear_k.weight"], W["linear_k.bias"]).reshape(B, Tk, n_head, dk).transpose(1, 2)
     v = linear(kv_in, W["linear_v.weight"], W["linear_v.bias"]).reshape(B, Tk, n_head, dk).transpose(1, 2)
+    if hook is not None:
+        q, k, v = hook(q, k, v)
     attn = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(dk), dim=-1)
     ctx = torch.matmul(attn, v).transpose(1, 2).reshape(B, Tq, D)
     return linear(ctx, W["linear_out.weight"], W["linear_out.bias"]), attn
@@ -197,9 +200,10 @@ def style_encoder(W, speech, cfg):
     return linear(ctx, M["linear_out.weight"], M["linear_out.bias"]).squeeze(1)
 
 
-def decoder_layer_step(W, tgt, memory, cache, n_head, normalize_before=True, concat_after=False):
+def decoder_layer_step(W, tgt, memory, cache, n_head, normalize_before=True, concat_after=False, attn_hook=None):
     """DecoderLayer.forward decoder_layer.py:74-158.
-    tgt (1, s, D); cache (1, s-1, D) or None.  Returns (x (1, s, D), src attention weights (H, T) of the last row)."""
+    tgt (1, s, D); cache (1, s-1, D) or None.  Returns (x (1, s, D), src attention weights (H, T) of the last row, self
+    attention weights (H, s) of the last row).  ``attn_hook``: see ``mha``; applied to both attentions."""
     residual = tgt
     t = layer_norm(tgt, W["norm1.weight"], W["norm1.bias"]) if normalize_before else tgt
     if cache is None:
@@ -207,7 +211,7 @@ def decoder_layer_step(W, tgt, memory, cache, n_head, normalize_before=True, con
     else:
         tq = t[:, -1:, :]
         residual = residual[:, -1:, :]
-    a = mha(W.sub("self_attn."), tq, t, n_head)[0]
+    a, self_attn = mha(W.sub("self_attn."), tq, t, n_head, attn_hook)
     if concat_after:                                                               # :126-129
         x = residual + linear(torch.cat([tq, a], dim=-1), W["concat_linear1.weight"], W["concat_linear1.bias"])
     else:
@@ -216,7 +220,7 @@ def decoder_layer_step(W, tgt, memory, cache, n_head, normalize_before=True, con
         x = layer_norm(x, W["norm1.weight"], W["norm1.bias"])
     residual = x
     h = layer_norm(x, W["norm2.weight"], W["norm2.bias"]) if normalize_before else x
-    a, attn = mha(W.sub("src_attn."), h, memory, n_head)
+    a, attn = mha(W.sub("src_attn."), h, memory, n_head, attn_hook)
     if concat_after:                                                               # :139-142
         x = residual + linear(torch.cat([h, a], dim=-1), W["concat_linear2.weight"], W["concat_linear2.bias"])
     else:
@@ -230,13 +234,15 @@ def decoder_layer_step(W, tgt, memory, cache, n_head, normalize_before=True, con
         x = layer_norm(x, W["norm3.weight"], W["norm3.bias"])
     if cache is not None:
         x = torch.cat([cache, x], dim=1)
-    return x, attn[0, :, -1]
+    return x, attn[0, :, -1], self_attn[0, :, -1]
 
 
 def inference(state, ids, cfg=None, threshold=0.5, minlenratio=0.0, maxlenratio=10.0, seed=0, drop="stream",
-              dtype=torch.float32, return_parts=False, spembs=None, speech=None):
+              dtype=torch.float32, return_parts=False, spembs=None, speech=None, attn_hook=None):
     """TransformerTTS.inference transformer_tts.py:511-647.  ids (T,) int64 without <eos>.
-    Returns (outs (L, odim), probs (L,), att_ws (dlayers, aheads, L, T+1))."""
+    Returns (outs (L, odim), probs (L,), att_ws (dlayers, aheads, L, T+1)).  With ``return_parts`` a dict too: ``hs``, ``enc``,
+    ``before``, ``zs`` and ``self_att``, per step the self-attention weights (dlayers, aheads, step) of the new row.
+    ``attn_hook``: a planted defect of the decoder's attentions (tests only), see ``mha``."""
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
     r = cfg.get("reduction_factor", 1)
     W = Weights(state, dtype)
@@ -260,7 +266,7 @@ def inference(state, ids, cfg=None, threshold=0.5, minlenratio=0.0, maxlenratio=
     D = W.sub("decoder.")
     idx = 0
     ys = torch.zeros(1, 1, odim, dtype=dtype)                                      # :601-602
-    outs, probs, att_ws = [], [], []
+    outs, probs, att_ws, self_ws = [], [], [], []
     cache = None
     parts = {}
     while True:
@@ -268,13 +274,16 @@ def inference(state, ids, cfg=None, threshold=0.5, minlenratio=0.0, maxlenratio=
         xdec = decoder_embed(D, ys, idx, cfg, drop)                                # decoder.py:210
         if cache is None:
             cache = [None] * cfg["dlayers"]
-        new_cache, att_step = [], []
+        new_cache, att_step, self_step = [], [], []
         for l in range(cfg["dlayers"]):                                            # decoder.py:214-218
-            xdec, a = decoder_layer_step(D.sub(f"decoders.{l}."), xdec, hs, cache[l], cfg["aheads"],
-                                         cfg.get("decoder_normalize_before", True), cfg.get("decoder_concat_after", False))
+            xdec, a, sa = decoder_layer_step(D.sub(f"decoders.{l}."), xdec, hs, cache[l], cfg["aheads"],
+                                             cfg.get("decoder_normalize_before", True), cfg.get("decoder_concat_after", False),
+                                             attn_hook)
             new_cache.append(xdec)
             att_step.append(a)
+            self_step.append(sa)
         cache = new_cache
+        self_ws.append(torch.stack(self_step, dim=0))                              # (dlayers, H, idx)
         z = xdec[:, -1]
         if cfg.get("decoder_normalize_before", True):
             z = layer_norm(z, D["after_norm.weight"], D["after_norm.bias"])        # decoder.py:220-221
@@ -295,6 +304,6 @@ def inference(state, ids, cfg=None, threshold=0.5, minlenratio=0.0, maxlenratio=
             break
     att = torch.stack(att_ws, dim=2)                                               # (dlayers, H, L, T)
     if return_parts:
-        parts.update(hs=hs[0], enc=enc_out[0], before=before[0].transpose(0, 1), zs=cache[-1][0])
+        parts.update(hs=hs[0], enc=enc_out[0], before=before[0].transpose(0, 1), zs=cache[-1][0], self_att=self_ws)
         return mel, probs_t, att, parts
     return mel, probs_t, att
