@@ -19,7 +19,8 @@
  *               TransformerTTSInference.forward :757-767
  *   pk_taco_*   parakeet/models/tacotron2.py Tacotron2.infer :781-840 (Tacotron2Decoder.infer :474-541),
  *               Tacotron2.forward :691-778 (Tacotron2Decoder.forward :419-472)
- *   pk_spk_*    parakeet/models/lstm_speaker_encoder.py LSTMSpeakerEncoder.embed_sequences / embed_utterance :40-53
+ *   pk_spk_*    parakeet/models/lstm_speaker_encoder.py LSTMSpeakerEncoder.embed_sequences / embed_utterance :40-53,
+ *               similarity_matrix :55-104 and the softmax loss :122-134 (pk_spk_ge2e; the EER :136-145 is host code)
  *   pk_stft_mel parakeet/modules/audio.py STFT.magnitude :202-215 + MelScale :226-229,
  *               parakeet/data/get_feats.py LogMelFBank.get_log_mel_fbank :80-88
  *
@@ -627,7 +628,8 @@ void pk_taco_destroy(pk_taco* h);
 
 /* ------------------------------------------------------- GE2E speaker encoder */
 /* LSTMSpeakerEncoder(n_mels, num_layers, hidden_size, output_size) -- parakeet/models/lstm_speaker_encoder.py:24-53
- * (released config examples/ge2e/config.py: 40, 3, 256, 256).  Inference only (embed_sequences / embed_utterance).
+ * (released config examples/ge2e/config.py: 40, 3, 256, 256).  Forward only: embed_sequences / embed_utterance and the GE2E
+ * similarity matrix and loss (no gradients).
  * Refused with PK_EUNSUPPORTED: hidden_size not a multiple of 32 or above 512, output_size not a multiple of 32 or above
  * 4096, n_mels above 4096. */
 typedef struct {
@@ -638,7 +640,8 @@ typedef struct pk_spk pk_spk;
 int pk_spk_create(pk_ctx* ctx, const pk_spk_cfg* cfg, pk_spk** out);
 /* set_state_dict entry: lstm.weight_ih_l{k} / weight_hh_l{k} / bias_ih_l{k} / bias_hh_l{k} (or their aliases
  * lstm.{k}.cell.weight_ih ...; the first form wins when both are given), linear.weight [in, out], linear.bias.
- * Other names (similarity_weight / similarity_bias: training only) are stored and ignored. */
+ * similarity_weight / similarity_bias (:29-32): shape [1] (else PK_ESHAPE), 10 and -5 unless set; read by pk_spk_ge2e, and
+ * setting them does not ask for another pk_spk_finalize.  Other names are stored and ignored. */
 int pk_spk_set_param(pk_spk* h, const char* name, const float* data, const int64_t* shape, int32_t ndim);
 /* 0 = exact fp32 MFMA, 1 = 3-term split-fp16 MFMA (default, as pk_taco_set_math). */
 int pk_spk_set_math(pk_spk* h, int32_t mode);
@@ -652,6 +655,23 @@ int pk_spk_finalize(pk_spk* h);
  * A partial's embedding does not depend on the other partials of the call. */
 int pk_spk_embed(pk_spk* h, const float* partials, int32_t P, int32_t T, const float* h0, const float* c0,
                  const int32_t* cu_partials, int32_t U, float* out);
+/* similarity_matrix (:55-104) and the softmax loss (:122-134) of embeds (N, M, C) float32 on the DEVICE: N speakers of M
+ * utterances, C dimensions, not assumed unit-norm.  Needs no pk_spk_finalize.  Outputs, each a DEVICE pointer or NULL
+ * (nothing is stored for a NULL one):
+ *   sim     (N*M, N)  p = (p1 with the own-speaker column replaced by p2) * similarity_weight + similarity_bias
+ *   p1      (N*M*N)   e . normalised inclusive centroid of every speaker
+ *   p2      (N*M)     e . normalised exclusive centroid (sum_m e - e) / (M - 1) of its own speaker
+ *   row_nll (N*M)     float64 logsumexp(p_row) - p_row[own speaker]
+ *   loss    (1)       float64 mean of the row terms
+ * fp32 sums in orders fixed by (M, C); permuting the speakers permutes sim, p1, p2 bit for bit; the fold is float64 in an
+ * order fixed by N*M; no atomics.  A centroid of zero norm gives NaN, as in the reference.
+ * PK_ESHAPE: N < 2, M < 2 (the exclusive centroid divides by M - 1) or C < 1.  PK_EUNSUPPORTED (never truncated): N > 4096,
+ * C > 2048, N*M > 2^20 or N*M*N > 2^28. */
+int pk_spk_ge2e(pk_spk* h, const float* embeds, int32_t N, int32_t M, int32_t C, float* sim, float* p1, float* p2,
+                double* row_nll, double* loss);
+/* out[u] = a[u] . b[u] / (max(|a[u]|, 1e-12) max(|b[u]|, 1e-12)) for u < U: the cosine similarity of two (U, C) float32 arrays
+ * of embeddings, all three on the DEVICE (how close a cloned voice is to its reference).  PK_ESHAPE: U < 1 or C < 1. */
+int pk_spk_cosine(pk_spk* h, const float* a, const float* b, int32_t U, int32_t C, float* out);
 void pk_spk_destroy(pk_spk* h);
 
 /* ------------------------------------------------- STFT / mel / log features */

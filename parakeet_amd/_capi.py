@@ -245,6 +245,8 @@ def _declare(lib):
         "pk_spk_set_math": (C.c_int, [vp, i32]),
         "pk_spk_finalize": (C.c_int, [vp]),
         "pk_spk_embed": (C.c_int, [vp, f32p, i32, i32, f32p, f32p, i32p, i32, f32p]),
+        "pk_spk_ge2e": (C.c_int, [vp, f32p, i32, i32, i32, f32p, f32p, f32p, C.c_void_p, C.c_void_p]),
+        "pk_spk_cosine": (C.c_int, [vp, f32p, f32p, i32, i32, f32p]),
         "pk_spk_destroy": (None, [vp]),
         "pk_mel_create": (C.c_int, [vp, C.POINTER(MelCfg), f32p, f32p, C.POINTER(vp)]),
         "pk_mel_num_frames": (C.c_int, [vp, i32, i32p]),

@@ -20,16 +20,21 @@
 //   PK_GEMM_MATH_F32 = exact fp32 on v_mfma_f32_32x32x2f32.
 // k_spk_head: relu(h(T) . W + b), normalise; optionally the per-utterance mean of the partials and a second normalise.
 //
+// pk_spk_ge2e: the GE2E similarity matrix and softmax loss over resident embeddings (similarity_matrix :55-104, loss
+// :122-134) -- kernels in spk_loss.hip; similarity_weight / similarity_bias ([1] each, 10 and -5 unless set) live here.
+//
 // LSTM semantics [paddle-semantics, from Paddle's API documentation]: gate order i, f, g, o along the 4H axis, zero
 // initial states unless given, c' = sigmoid(f) c + sigmoid(i) tanh(g), h' = sigmoid(o) tanh(c').
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "pk_fft.h"
 #include "pk_mfma.h"
 #include "pk_split.h"
+#include "pk_spk_loss.h"
 
 namespace {
 typedef pk_fft_dense Dense;
@@ -289,6 +294,7 @@ struct pk_spk : pk_fft_core {
     std::vector<int> kw;                // per layer: exponent of the split weights
     size_t lin_w = 0, lin_b = 0;
     pk_dbuf d_x, d_xg, d_hseq, d_hlast, d_cu;
+    pk_dbuf d_ge2e;                     // pk_spk_ge2e: row terms, speaker sums, transposed centroids
     std::vector<int32_t> cu_h;          // host copy of the last call's utterance bounds (source of its async copy)
     hipEvent_t cu_ev = nullptr;         // recorded after that copy
 };
@@ -331,6 +337,13 @@ extern "C" int pk_spk_create(pk_ctx* ctx, const pk_spk_cfg* cfg, pk_spk** out) {
 
 extern "C" int pk_spk_set_param(pk_spk* h, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
     if (!h) PK_FAIL(PK_EINVAL, "pk_spk_set_param: handle is NULL");
+    if (name && (!strcmp(name, "similarity_weight") || !strcmp(name, "similarity_bias"))) {
+        // the GE2E scale and offset (:29-32): read by pk_spk_ge2e, no part of the packed weights
+        int64_t n = 1;
+        for (int i = 0; i < ndim; ++i) n *= shape ? shape[i] : 0;
+        if (!data || !shape || ndim < 1 || n != 1) PK_FAIL(PK_ESHAPE, "LSTMSpeakerEncoder: parameter %s must have shape [1]", name);
+        return pk_store_param(h->params, name, data, shape, ndim);
+    }
     h->finalized = false;
     return pk_store_param(h->params, name, data, shape, ndim);
 }
@@ -504,12 +517,29 @@ extern "C" int pk_spk_embed(pk_spk* h, const float* partials, int32_t P, int32_t
     return PK_OK;
 }
 
+extern "C" int pk_spk_ge2e(pk_spk* h, const float* embeds, int32_t N, int32_t M, int32_t C, float* sim, float* p1, float* p2,
+                           double* row_nll, double* loss) {
+    if (!h || !embeds) PK_FAIL(PK_EINVAL, "pk_spk_ge2e: NULL argument");
+    float wb[2] = {10.f, -5.f};   // I.Constant(10.), I.Constant(-5.) (:29-32)
+    const char* names[2] = {"similarity_weight", "similarity_bias"};
+    for (int i = 0; i < 2; ++i) {
+        auto it = h->params.find(names[i]);
+        if (it != h->params.end()) wb[i] = it->second.data[0];
+    }
+    return pk_spk_loss_run(h->ctx, h->d_ge2e, wb[0], wb[1], embeds, N, M, C, sim, p1, p2, row_nll, loss);
+}
+
+extern "C" int pk_spk_cosine(pk_spk* h, const float* a, const float* b, int32_t U, int32_t C, float* out) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_spk_cosine: handle is NULL");
+    return pk_spk_cosine_run(h->ctx, a, b, U, C, out);
+}
+
 extern "C" void pk_spk_destroy(pk_spk* h) {
     if (!h) return;
     pk_device_guard _dg(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
     h->release_core();
-    pk_dbuf* bufs[] = {&h->d_x, &h->d_xg, &h->d_hseq, &h->d_hlast, &h->d_cu};
+    pk_dbuf* bufs[] = {&h->d_x, &h->d_xg, &h->d_hseq, &h->d_hlast, &h->d_cu, &h->d_ge2e};
     for (auto* b : bufs) b->release();
     if (h->cu_ev) (void)hipEventDestroy(h->cu_ev);
     delete h;
