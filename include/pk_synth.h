@@ -321,7 +321,10 @@ typedef struct {
     int32_t upsample_factors[4];   /* 16, 16 */
     int32_t n_flows;               /* 8, even (:586-589) */
     int32_t n_layers;              /* 8 = len(dilations_dict[n_group]) (:328-331) */
-    int32_t n_group;               /* 16, even */
+    int32_t n_group;               /* 8, 16, 32, 64 or 128: the keys of Flow.dilations_dict (:420-426), which gives residual layer l
+                                    * its height dilation -- 1 for every layer up to 16; 1 2 4 1 2 4 1 2 at 32; 1 2 4 8 16 1 2 4 at
+                                    * 64; 1 2 4 8 16 32 64 1 at 128.  Another even value: PK_EUNSUPPORTED (a KeyError there); odd:
+                                    * PK_EINVAL (:586-589) */
     int32_t channels;              /* 64 (paper small model) / 128 (repo default) */
     int32_t n_mels;                /* 80 */
     int32_t kernel_h, kernel_w;    /* 3, 3 */
@@ -345,7 +348,7 @@ int pk_wf_set_math(pk_wf* h, int32_t mode);
  *                  packed fp32 FMA with op_sel, DESIGN.md 4.3 "the op_sel rule" -- and every configuration is back.)
  *   "persistent"   0 only.  (1 = the layers of a row in ONE cooperative launch with a barrier across the grid between two layers:
  *                  measured slower than eight launches in round 4; PK_EUNSUPPORTED in the product, a measurement configuration of
- *                  the profile build)
+ *                  the profile build, and there for n_group 8 / 16 only: the launch has one tap table for all its layers)
  *   "fuse_step"    1 (default) = a row's affine step and the next row's input projection happen in the launch of its last
  *                  layer; 0 = in a kernel of their own */
 int pk_wf_set_option(pk_wf* h, const char* key, int64_t value);
@@ -359,11 +362,15 @@ int pk_wf_cond_length(pk_wf* h, int32_t t_mel, int32_t* cond_len, int32_t* wav_l
  *   frames (B) host int32, >= 2
  *   z      packed latent, cond_len(frames[b]) floats per utterance (the randn of :801);
  *          NULL = drawn internally (pk_randn stream of pk_wf_set_seed)
- *   wav    packed output, wav_len(frames[b]) floats per utterance */
+ *   wav    packed output, wav_len(frames[b]) floats per utterance
+ * Every n_group of pk_wf_cfg: a layer with height dilation dh looks back at the rows i - dh and i - 2 dh of its own input, kept in
+ * a ring of min(2 dh + 1, n_group) rows per layer -- the workspace is sum of the rings (25 rows of positions x channels floats
+ * up to n_group 16, 264 at n_group 128) and the launch count n_flows x (n_group - 1) x n_layers whatever the dilations. */
 int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, int32_t B, const float* z,
                 float* wav, int32_t flags);
 /* ConditionalWaveFlow.forward (:759-782): density estimation, audio -> (z, log-determinant), for a packed ragged batch.  Not
- * autoregressive: a layer of a flow runs on all n_group - 1 rows in one launch (n_flows x n_layers dependent layer launches).
+ * autoregressive: a layer of a flow runs on all n_group - 1 rows in one launch (n_flows x n_layers dependent layer launches, for
+ * every n_group: the rows lie behind 2 x the largest height dilation rows of zeros, the conv's causal padding).
  *   mel, frames  as pk_wf_infer (frames >= 1); the condition is the UNTRIMMED upsampled mel (:780), frames[b] * prod(factors) long
  *   audio        packed, audio_len[b] floats per utterance; n_group <= audio_len[b] <= frames[b] * prod(factors) (_trim :617-625),
  *                else PK_EINVAL

@@ -90,7 +90,9 @@ struct WflLaunch {
     const float* cond;       // condition row (planes, 96 channels)
     const unsigned* cond_amax;
     int ntap;                // conv taps whose input row exists (3, 6 or 9)
-    int tap_slot[9], tap_col[9], tap_w[9];   // ring slot, kernel column - 1 (-1, 0, 1), weight tap index kr*3 + kc
+    int tap_slot[9], tap_col[9], tap_w[9];   // ring slot, kernel column - 1 (-1, 0, 1), weight tap index kr*3 + kc.  A slot is any
+                             // non-negative row of the ring (a layer with height dilation dh has min(2 dh + 1, n_group) of them): the
+                             // kernel forms slot * slot_stride and slot * amax_stride in 64 bits (tp_off, tp_am, the cur_slot address)
     const int* pos_utt;      // [npos_alloc] utterance of a position, < 0: gap (outputs forced to 0)
     int npos_alloc;          // multiple of 32
     unsigned long long* trace;  // profiling only (PK_WF_ABLATE=16): s_memtime stamps of workgroup 5, [wave 8][round 2][24]
@@ -131,8 +133,9 @@ int wfl_step_launch(pk_ctx* ctx, int C, const float* prm, float b_logs, float b_
 
 // ---- the forward direction (pk_wf_forward): the rows of a flow as "flat" rows, one behind the other on one position axis, so that
 // ONE wfl_layer_launch covers every (row, 32-position tile) of a layer: slot_stride = the positions of a row * C, tap_slot = the
-// kernel row, npos_alloc = rows * positions of a row, in0 = a buffer that starts with two rows of zeros (the rows before the first).
-constexpr int WFL_MAX_ROWS = 16;
+// row (2 - kernel row) * the layer's height dilation rows back, npos_alloc = rows * positions of a row, in0 = a buffer that starts
+// with 2 * the largest height dilation rows of zeros (the rows before the first).
+constexpr int WFL_MAX_ROWS = 128;   // the largest n_group (Flow.dilations_dict); the maps travel by value, 512 bytes of kernel arguments
 struct WflRowMap { int row[WFL_MAX_ROWS]; };
 // dst row r (planes, block maxima in amax) = src row map.row[r] (fp32 [pos / 32][96][32]); channel n_mels := 1 (see above)
 int wfl_cond_planes_rows_launch(pk_ctx* ctx, const float* src, long src_row_stride, float* dst, long dst_row_stride, unsigned* amax,

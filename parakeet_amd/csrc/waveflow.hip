@@ -10,12 +10,14 @@
 // a batch share one position axis ("width timeline") framed by GAPW >= 2^(n_layers-1) zero positions,
 // so the width-dilated "same" convolutions see the reference's zero padding and ragged batches are
 // exact.  Per-position feature rows are channels-last [pos][C] fp32, i.e. GEMM A operands:
-//   hist[l][slot][pos][C]   inputs of residual layer l for the last 3 rows (the reference's
-//                           _conv_buffer, kept as a ring instead of concat-shifting every step)
+//   hist[l][slot][pos][C]   inputs of residual layer l for the last 2 dh_l + 1 rows (the reference's
+//                           _conv_buffer, kept as a ring instead of concat-shifting every step; dh_l = the
+//                           layer's height dilation, Flow.dilations_dict :420-426 -- 1 up to n_group 16)
 //   cond[h][pos][n_mels]    upsampled mel, folded; row permutations of the flows are index maps
 //   cur/nxt[h][pos]         the folded latent / signal
 // One autoregressive step (flow f, row i) = for each of the 8 layers: GEMM1 (3x3 dilated causal conv
-// as <=9 shifted taps + condition_proj as a second K block, gated-tanh epilogue) -> GEMM2 (out_proj,
+// as <=9 shifted taps -- kernel row kr reads step i - (2 - kr) dh_l -- + condition_proj as a second K block,
+// gated-tanh epilogue) -> GEMM2 (out_proj,
 // residual into the next layer's ring slot, skip accumulated), then k_wf_step (output_proj, affine
 // inverse, input_proj of the new row).  Rows that do not exist yet (steps < 1) are skipped as taps
 // instead of being stored as zeros.
@@ -249,6 +251,13 @@ struct pk_wf {
     pk_param_map params;
     bool finalized = false;
     int gapw = 128;
+    // height dilation of every residual layer (Flow.dilations_dict :420-426) and the layers' input rings: layer l keeps the last
+    // ring[l] = min(2 dil_h[l] + 1, n_group) rows of its input at the slots [slot_base[l], slot_base[l] + ring[l]) of ws_hist; the
+    // entry past the last layer is the one slot the unfused path's last out projection writes (and nobody reads, :390)
+    int dil_h[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    int ring[9] = {3, 3, 3, 3, 3, 3, 3, 3, 1};
+    int slot_base[9] = {0};
+    int nslots = 25, dh_max = 1;
     std::vector<float> arena_h;
     pk_dbuf arena;
     std::vector<uint16_t> arena16_h;
@@ -281,8 +290,13 @@ extern "C" int pk_wf_create(pk_ctx* ctx, const pk_wf_cfg* cfg, pk_wf** out) {
     if (c.n_group % 2 || c.n_flows % 2 || c.n_group <= 0 || c.n_flows <= 0)
         PK_FAIL(PK_EINVAL, "number of flows and number of group must be even since a permutation along "
                            "group among flows is used.");  // waveflow.py:586-589 (ValueError)
-    if (c.n_group != 8 && c.n_group != 16)
-        PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: n_group %d needs height dilations > 1 (not implemented)", c.n_group);
+    // Flow.dilations_dict :420-426 (any other n_group is a KeyError there)
+    static const int wf_dilations_h[5][9] = {{8, 1, 1, 1, 1, 1, 1, 1, 1},   {16, 1, 1, 1, 1, 1, 1, 1, 1},   {32, 1, 2, 4, 1, 2, 4, 1, 2},
+                                             {64, 1, 2, 4, 8, 16, 1, 2, 4}, {128, 1, 2, 4, 8, 16, 32, 64, 1}};
+    const int* dil_h = nullptr;
+    for (const auto& row : wf_dilations_h)
+        if (row[0] == c.n_group) dil_h = row + 1;
+    if (!dil_h) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: n_group %d has no height dilations (8, 16, 32, 64 or 128)", c.n_group);
     if (c.n_layers != 8) PK_FAIL(PK_EINVAL, "number of dilations_h should equals num of layers");  // :328-331
     if (c.kernel_h != 3 || c.kernel_w != 3) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: kernel_size must be (3, 3)");
     if (c.channels % 64 != 0 || c.channels > 256) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: channels must be 64/128/192/256");
@@ -295,6 +309,19 @@ extern "C" int pk_wf_create(pk_ctx* ctx, const pk_wf_cfg* cfg, pk_wf** out) {
     h->ctx = ctx;
     h->cfg = c;
     h->gapw = 1 << (c.n_layers - 1);
+    h->nslots = 0;
+    h->dh_max = 1;
+    for (int l = 0; l <= c.n_layers; ++l) {
+        if (l < c.n_layers) {
+            h->dil_h[l] = dil_h[l];
+            h->ring[l] = std::min(2 * dil_h[l] + 1, c.n_group);
+            h->dh_max = std::max(h->dh_max, dil_h[l]);
+        } else {
+            h->ring[l] = 1;
+        }
+        h->slot_base[l] = h->nslots;
+        h->nslots += h->ring[l];
+    }
     h->mp = ((c.n_mels + PK_GEMM_HBK - 1) / PK_GEMM_HBK) * PK_GEMM_HBK;
     if (const char* e = pk_prof_env("PK_WF_MATH")) h->math = strcmp(e, "f32") == 0 ? PK_GEMM_MATH_F32 : PK_GEMM_MATH_F16X3;
     *out = h;
@@ -350,6 +377,8 @@ extern "C" int pk_wf_set_option(pk_wf* h, const char* key, int64_t value) {
         // sizes beyond the tests' it is not deterministic either (tools/wf_race_bisect.py: thousands of samples off by 1e-3 per
         // call).  The product refuses it; the profile build keeps it for the barrier measurements.
         if (value != 0 && !wfl_measurement_configs_allowed()) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_set_option: 'persistent' is not in the product (not deterministic beyond small sizes)");
+        // one launch carries ONE tap table for its layers: with height dilations the rows a layer looks back at differ per layer
+        if (value != 0 && h->dh_max > 1) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_set_option: 'persistent' runs the layers of a row with one tap table (n_group 8 / 16 only)");
         h->persistent = value != 0;
     }
     else if (strcmp(key, "fuse_step") == 0) h->fuse_step = value != 0;
@@ -526,7 +555,11 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
         Wb[b] = pruned[b] / G;
         if (Wb[b] <= 0) PK_FAIL(PK_EINVAL, "pk_wf_infer: utterance %d too short", b);
         woff[b] = pos;
-        pos += Wb[b] + h->gapw;
+        // With height dilations (n_group >= 32) utterances start at multiples of 32 positions, as in pk_wf_forward: the 32-position
+        // scale blocks then fall at the same places inside an utterance and no tile of one utterance reads a block of another
+        // (128 gap positions past the rounded end: a tile's widest tap reaches 128 + 31 positions) -- an utterance's waveform is
+        // the same bit for bit in any batch.  n_group 8 / 16 keep the packing (and the bits) they always had.
+        pos = (h->dh_max > 1 ? (pos + Wb[b] + 31) / 32 * 32 : pos + Wb[b]) + h->gapw;
         zoff[b] = (int)sumZ;
         ooff[b] = (int)sumO;
         sumZ += clen[b];
@@ -606,7 +639,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     PK_TRY(h->ws_cond.reserve((size_t)G * cond_row * 4));
     PK_TRY(h->ws_cur.reserve((size_t)G * pstride * 4));
     PK_TRY(h->ws_nxt.reserve((size_t)G * pstride * 4));
-    PK_TRY(h->ws_hist.reserve((size_t)(NL + 1) * 3 * feat_row * 4));
+    PK_TRY(h->ws_hist.reserve((size_t)h->nslots * feat_row * 4));
     PK_TRY(h->ws_zbuf.reserve((size_t)feat_row * 4));
     PK_TRY(h->ws_skip.reserve((size_t)feat_row * 4));
     // block scaling of the split-fp16 GEMMs (pk_split.h): max|row| of every hist / cond row, kept next to the data
@@ -616,14 +649,14 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     const long bstride = pstride / WFL_BLK;   // blocks per buffer row incl. margins
     PK_TRY(h->ws_bar.reserve(2 * sizeof(unsigned)));   // grid barrier counter | its time-out flag (pk_grid.h)
     PK_HIP(hipMemsetAsync(h->ws_bar.p, 0, 2 * sizeof(unsigned), ctx->stream));
-    PK_TRY(h->ws_hamax.reserve((size_t)(NL + 1) * 3 * pstride * 4));
+    PK_TRY(h->ws_hamax.reserve((size_t)h->nslots * pstride * 4));
     PK_TRY(h->ws_camax.reserve((size_t)G * pstride * 4));
-    PK_HIP(hipMemsetAsync(h->ws_hamax.p, 0, (size_t)(NL + 1) * 3 * pstride * 4, ctx->stream));
+    PK_HIP(hipMemsetAsync(h->ws_hamax.p, 0, (size_t)h->nslots * pstride * 4, ctx->stream));
     PK_HIP(hipMemsetAsync(h->ws_camax.p, 0, (size_t)G * pstride * 4, ctx->stream));
     for (int i = 0; i + 1 < c.n_upsample; ++i) PK_TRY(h->ws_u[i & 1].reserve((size_t)layer_rows[i + 1] * M * 4));
     // cond gaps / margins are read by masked rows only, but must be finite
     PK_HIP(hipMemsetAsync(h->ws_cond.p, 0, (size_t)G * cond_row * 4, ctx->stream));
-    PK_HIP(hipMemsetAsync(h->ws_hist.p, 0, (size_t)(NL + 1) * 3 * feat_row * 4, ctx->stream));
+    PK_HIP(hipMemsetAsync(h->ws_hist.p, 0, (size_t)h->nslots * feat_row * 4, ctx->stream));
     PK_HIP(hipMemsetAsync(h->ws_zbuf.p, 0, (size_t)feat_row * 4, ctx->stream));
     float* cond = h->ws_cond.as<float>() + (size_t)WF_LEAD * MP;
     float* cur = h->ws_cur.as<float>() + WF_LEAD;
@@ -632,10 +665,10 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     float* zbuf = h->ws_zbuf.as<float>() + (size_t)WF_LEAD * C;
     float* skip = h->ws_skip.as<float>() + (size_t)WF_LEAD * C;
     float* prm = skip;   // the fused path keeps two floats per position here instead of C
-    auto hist_ptr = [&](int layer, int slot) { return hist + ((size_t)layer * 3 + slot) * feat_row; };
+    auto hist_ptr = [&](int layer, int slot) { return hist + ((size_t)h->slot_base[layer] + slot) * feat_row; };   // slot < ring[layer]
     float* hamax = h->ws_hamax.as<float>() + WF_LEAD;
     float* camax = h->ws_camax.as<float>() + WF_LEAD;
-    auto hamax_ptr = [&](int layer, int slot) { return hamax + ((size_t)layer * 3 + slot) * pstride; };
+    auto hamax_ptr = [&](int layer, int slot) { return hamax + ((size_t)h->slot_base[layer] + slot) * pstride; };
     const bool split_math = h->math == PK_GEMM_MATH_F16X3;
 
     // ---- upsample (encoder)
@@ -663,7 +696,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     }
     unsigned* hbmax = h->ws_hamax.as<unsigned>() + WF_LEAD / WFL_BLK;   // block maxima (fused layer kernel)
     unsigned* cbmax = h->ws_camax.as<unsigned>() + WF_LEAD / WFL_BLK;
-    auto hbmax_ptr = [&](int layer, int slot) { return hbmax + ((size_t)layer * 3 + slot) * bstride; };
+    auto hbmax_ptr = [&](int layer, int slot) { return hbmax + ((size_t)h->slot_base[layer] + slot) * bstride; };
     if (use_wfl) PK_TRY(wfl_cond_planes_launch(ctx, cond, cond_row, G, npos_alloc / WFL_BLK, bstride, cbmax, M));   // in place
     else if (split_math) PK_TRY(pk_row_amax_launch(ctx, cond, MP, MP, 0, (long)G * pstride - WF_LEAD, camax));
     // ---- fold z
@@ -686,15 +719,18 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     static const char* replay_env = pk_prof_env("PK_WF_REPLAY");   // "<launch>:<repeats>" (see k_wf_replay_compare)
     const int replay_seq = replay_env ? atoi(replay_env) : -1;
     const int replay_reps = replay_env && strchr(replay_env, ':') ? atoi(strchr(replay_env, ':') + 1) : 0;
-    // ---- the layer descriptors of the fused kernel, one per (flow, ring slot of the current row, layer): weights of the
-    // (flow, layer), input ring of the layer, output = the next layer's ring at the current row's slot
+    // ---- the layer descriptors of the fused kernel, one per (flow, row, layer): weights of the (flow, layer), input ring of the
+    // layer, output = the next layer's ring at the current row's slot THERE (the rings differ in depth once a layer has a height
+    // dilation, so the slot depends on the row and the layer, not on the row alone)
+    auto ring_slot = [&](int layer, int step) { return step % h->ring[layer]; };   // step >= 0
     if (use_wfl) {
-        h->desc_host.assign((size_t)c.n_flows * 3 * NL, WflLayer());
+        h->desc_host.assign((size_t)c.n_flows * G * NL, WflLayer());
         for (int fl = 0; fl < c.n_flows; ++fl)
-            for (int slot = 0; slot < 3; ++slot)
+            for (int row = 1; row < G; ++row)
                 for (int l = 0; l < NL; ++l) {
                     const WfLayerW& L = h->flows[fl].layers[l];
-                    WflLayer& wl = h->desc_host[((size_t)fl * 3 + slot) * NL + l];
+                    WflLayer& wl = h->desc_host[((size_t)fl * G + row) * NL + l];
+                    const int slot = l + 1 < NL ? ring_slot(l + 1, row) : 0;
                     wl.w.w1 = h->arena16.as<uint16_t>() + L.fl.w1;
                     wl.w.w2 = h->arena16.as<uint16_t>() + L.fl.w2;
                     wl.w.b2r = h->W(L.fl.b2r);
@@ -723,20 +759,30 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
         for (int i = 0; i < G; ++i) cnew[i] = cidx[perm[i]];   // cumulative shuffle of the condition
         cidx = cnew;
         const WfFlowW& F = h->flows[fl];
-        // row 0: copy + input_proj into slot 1 of layer 0
+        // row 0: copy + input_proj into the slot of step 1 of layer 0
+        const int slot1 = ring_slot(0, 1);
         if (use_wfl) {
             PK_TRY(wfl_step_launch(ctx, C, prm, F.b_logs_f, F.b_b_f, cur + (long)perm[0] * pstride, nxt,
-                                   h->W(F.w_in), h->W(F.b_in), hist_ptr(0, 1), hbmax_ptr(0, 1), rowvalid, npos_alloc, 1));
+                                   h->W(F.w_in), h->W(F.b_in), hist_ptr(0, slot1), hbmax_ptr(0, slot1), rowvalid, npos_alloc, 1));
         } else {
         PK_LAUNCH(ctx, "wf_step", k_wf_step, dim3(pk_div_up(npos, 4)), dim3(256), 0, skip, C, h->W(F.w_out), F.b_logs,
-                  F.b_b, cur + (long)perm[0] * pstride, nxt, h->W(F.w_in), h->W(F.b_in), hist_ptr(0, 1), rowvalid,
+                  F.b_b, cur + (long)perm[0] * pstride, nxt, h->W(F.w_in), h->W(F.b_in), hist_ptr(0, slot1), rowvalid,
                   npos, 1);
-        if (split_math) PK_TRY(pk_row_amax_launch(ctx, hist_ptr(0, 1), C, C, 0, npos, hamax_ptr(0, 1)));
+        if (split_math) PK_TRY(pk_row_amax_launch(ctx, hist_ptr(0, slot1), C, C, 0, npos, hamax_ptr(0, slot1)));
         }
         // the fused kernel needs the 64-channel shape (one 128-column block) and the split-fp16 path
         const bool fuse_proj = C == 64 && h->math == PK_GEMM_MATH_F16X3 && MP % PK_GEMM_HBK == 0 && !h->no_fuse;
+        // The taps of (row i, layer l): kernel row kr reads the layer's input of step i - (2 - kr) dh_l, a slot of the layer's
+        // ring; steps before the sequence start are the zero rows of the reference's _conv_buffer (:287-290) and are skipped.
+        // The step grows with kr, so the rows skipped are the FIRST kernel rows and the taps present are the last ntap of the
+        // nine, in order -- what the fused kernel's linear weight addressing needs (wfl_layer_launch checks tap_w).
+        auto first_kr = [&](int i, int l) {
+            int kr = 0;
+            while (i - (2 - kr) * h->dil_h[l] < 1) ++kr;   // kr = 2 reads step i >= 1
+            return kr;
+        };
         for (int i = 1; i < G; ++i) {
-            const int slot = i % 3;
+            const int h0slot = ring_slot(0, i + 1);   // layer 0's slot of the next row
             if (use_wfl) {
                 // the fused layer kernel (wf_layer.hip): conv taps + condition + gate + res projection + folded skip path.
                 // One launch runs `per` consecutive layers of this row: all NL behind grid barriers (option "persistent",
@@ -748,21 +794,20 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 w.f16 = h->math == PK_GEMM_MATH_F16;
                 w.slot_stride = feat_row;
                 w.amax_stride = bstride;
-                w.cur_slot = slot;
                 w.prm = prm;
                 w.cond = cond + (long)cidx[i] * cond_row;
                 w.cond_amax = cbmax + (long)cidx[i] * bstride;
-                w.ntap = 0;
-                for (int kr = 0; kr < 3; ++kr) {
-                    const int step = i - 2 + kr;   // kernel row kr reads the layer input of this step
-                    if (step < 1) continue;        // rows before the sequence start are zeros (:287-290)
-                    for (int kc = 0; kc < 3; ++kc) {
-                        w.tap_slot[w.ntap] = step % 3;
-                        w.tap_col[w.ntap] = kc - 1;
-                        w.tap_w[w.ntap] = kr * 3 + kc;
-                        ++w.ntap;
-                    }
-                }
+                auto set_taps = [&](int l) {   // the tap table and the current slot of layer l
+                    w.cur_slot = ring_slot(l, i);
+                    w.ntap = 0;
+                    for (int kr = first_kr(i, l); kr < 3; ++kr)
+                        for (int kc = 0; kc < 3; ++kc) {
+                            w.tap_slot[w.ntap] = ring_slot(l, i - (2 - kr) * h->dil_h[l]);
+                            w.tap_col[w.ntap] = kc - 1;
+                            w.tap_w[w.ntap] = kr * 3 + kc;
+                            ++w.ntap;
+                        }
+                };
                 w.pos_utt = rowvalid;
                 w.npos_alloc = npos_alloc;
                 w.trace = d_trace;
@@ -773,18 +818,19 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 const bool persistent = h->persistent && pk_grid_available() && NL <= WFL_MAX_LAYERS && !d_trace;
                 const int per = persistent ? NL : 1;
                 const bool fuse = h->fuse_step && C == 64;   // (the 128-channel kernel has no registers for the fused step)
-                float* h0n = (i + 1 < G) ? hist_ptr(0, (i + 1) % 3) : nullptr;
+                float* h0n = (i + 1 < G) ? hist_ptr(0, h0slot) : nullptr;
                 for (int l0 = 0; l0 < NL; l0 += per) {
                     w.nl = per;
-                    w.layers = h->ws_desc.as<WflLayer>() + ((size_t)(fl * 3 + slot) * NL + l0);   // (flow, ring slot, layer)
-                    w.l0 = h->desc_host[(size_t)(fl * 3 + slot) * NL + l0];                        // ... and its host image (per == 1)
+                    set_taps(l0);   // (per > 1, option "persistent": refused unless every layer has this table, pk_wf_set_option)
+                    w.layers = h->ws_desc.as<WflLayer>() + (((size_t)fl * G + i) * NL + l0);   // (flow, row, layer)
+                    w.l0 = h->desc_host[((size_t)fl * G + i) * NL + l0];                        // ... and its host image (per == 1)
                     if (l0 + per == NL && fuse) {
                         w.step_z = cur + (long)perm[i] * pstride;
                         w.step_x = nxt + (long)i * pstride;
                         w.step_w_in = h->W(F.w_in);
                         w.step_b_in = h->W(F.b_in);
                         w.step_h0 = h0n;
-                        w.step_h0_amax = h0n ? hbmax_ptr(0, (i + 1) % 3) : nullptr;
+                        w.step_h0_amax = h0n ? hbmax_ptr(0, h0slot) : nullptr;
                         w.step_b_logs = F.b_logs_f;
                         w.step_b_b = F.b_b_f;
                     }
@@ -852,7 +898,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 if (!fuse)
                     PK_TRY(wfl_step_launch(ctx, C, prm, F.b_logs_f, F.b_b_f, cur + (long)perm[i] * pstride,
                                            nxt + (long)i * pstride, h->W(F.w_in), h->W(F.b_in), h0n,
-                                           h0n ? hbmax_ptr(0, (i + 1) % 3) : nullptr, rowvalid, npos_alloc, 0));
+                                           h0n ? hbmax_ptr(0, h0slot) : nullptr, rowvalid, npos_alloc, 0));
                 continue;
             }
             for (int l = 0; l < NL && !use_wfl; ++l) {
@@ -863,15 +909,13 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 g.Cin = C;
                 g.ntaps = 0;
                 const long dil = 1L << l;
-                for (int kr = 0; kr < 3; ++kr) {
-                    const int step = i - 2 + kr;   // kernel row kr reads the layer input of this step
-                    if (step < 1) continue;        // rows before the sequence start are zeros (:287-290)
+                const int slot = ring_slot(l, i), oslot = ring_slot(l + 1, i);   // the row's slot in this layer's ring and in the next one's
+                for (int kr = first_kr(i, l); kr < 3; ++kr)
                     for (int kc = 0; kc < 3; ++kc) {
-                        g.tap_off[g.ntaps] = (long)(step % 3) * feat_row + (long)(kc - 1) * dil * C;
+                        g.tap_off[g.ntaps] = (long)ring_slot(l, i - (2 - kr) * h->dil_h[l]) * feat_row + (long)(kc - 1) * dil * C;
                         g.tap_w[g.ntaps] = kr * 3 + kc;
                         ++g.ntaps;
                     }
-                }
                 g.a_amax = hamax_ptr(l, 0);
                 g.a2_amax = camax + (long)cidx[i] * pstride;
                 g.A2 = cond + (long)cidx[i] * cond_row;
@@ -893,14 +937,14 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                     g.bias2 = h->W(L.b2);
                     g.res = hist_ptr(l, slot);
                     g.ldr = C;
-                    g.C = hist_ptr(l + 1, slot);
+                    g.C = hist_ptr(l + 1, oslot);
                     g.ldc = C;
                     g.nsplit = C;
                     g.C2 = skip;
                     g.ldc2 = C;
                     g.acc2 = l > 0;
                     PK_TRY(pk_gemm_launch(ctx, "wf_gemm_conv_gate_proj", g));
-                    if (l + 1 < NL) PK_TRY(pk_row_amax_launch(ctx, hist_ptr(l + 1, slot), C, C, 0, npos, hamax_ptr(l + 1, slot)));
+                    if (l + 1 < NL) PK_TRY(pk_row_amax_launch(ctx, hist_ptr(l + 1, oslot), C, C, 0, npos, hamax_ptr(l + 1, oslot)));
                     continue;
                 }
                 g.epi = PK_EPI_GATE;
@@ -919,7 +963,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 o.bias = h->W(L.b2);
                 o.res = hist_ptr(l, slot);
                 o.ldr = C;
-                o.C = hist_ptr(l + 1, slot);
+                o.C = hist_ptr(l + 1, oslot);
                 o.ldc = C;
                 o.nsplit = C;
                 o.C2 = skip;
@@ -930,13 +974,13 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                 o.N = 2 * C;
                 PK_TRY(pk_gemm_launch(ctx, "wf_gemm_out_proj", o));
                 if (split_math && l + 1 < NL)
-                    PK_TRY(pk_row_amax_launch(ctx, hist_ptr(l + 1, slot), C, C, 0, npos, hamax_ptr(l + 1, slot)));
+                    PK_TRY(pk_row_amax_launch(ctx, hist_ptr(l + 1, oslot), C, C, 0, npos, hamax_ptr(l + 1, oslot)));
             }
-            float* h0n = (i + 1 < G) ? hist_ptr(0, (i + 1) % 3) : nullptr;
+            float* h0n = (i + 1 < G) ? hist_ptr(0, h0slot) : nullptr;
             PK_LAUNCH(ctx, "wf_step", k_wf_step, dim3(pk_div_up(npos, 4)), dim3(256), 0, skip, C, h->W(F.w_out),
                       F.b_logs, F.b_b, cur + (long)perm[i] * pstride, nxt + (long)i * pstride, h->W(F.w_in),
                       h->W(F.b_in), h0n, rowvalid, npos, 0);
-            if (split_math && h0n) PK_TRY(pk_row_amax_launch(ctx, h0n, C, C, 0, npos, hamax_ptr(0, (i + 1) % 3)));
+            if (split_math && h0n) PK_TRY(pk_row_amax_launch(ctx, h0n, C, C, 0, npos, hamax_ptr(0, h0slot)));
         }
         std::swap(cur, nxt);
     }
@@ -1002,9 +1046,9 @@ extern "C" int pk_wf_forward_length(pk_wf* h, int32_t t_mel, int32_t n_audio, in
 
 // ConditionalWaveFlow.forward :759-782 = UpsampleNet (untrimmed, :780) + WaveFlow.forward :627-672.  Every row of the folded audio is
 // known, so Flow.forward (:491-493) runs the ResidualNet on rows 0 .. G-2 with condition rows 1 .. G-1 AT ONCE: the rows of a flow
-// lie one behind the other on one position axis ("flat" rows) behind two rows of zeros (the rows before the first: the causal
-// (3, 3) conv's padding in height, :229-236), and a layer of a flow is ONE launch of the fused layer kernel over all G - 1 rows
-// with all nine taps -- n_flows x n_layers dependent layer launches per call instead of infer's n_flows x (G - 1) x n_layers.
+// lie one behind the other on one position axis ("flat" rows) behind Z = 2 max_l dh_l rows of zeros (the rows before the first: the
+// causal (3, 3) conv's padding in height, rh - 1 = 2 dh_l rows, :229-236 -- two rows up to n_group 16), and a layer of a flow is ONE
+// launch of the fused layer kernel over all G - 1 rows with all nine taps, kernel row kr (2 - kr) dh_l rows before the tile's own -- n_flows x n_layers dependent layer launches per call instead of infer's n_flows x (G - 1) x n_layers.
 // Two such buffers, ping-ponged between the layers (a layer reads positions other workgroups write).
 // Utterances start at multiples of 32 positions with at least 192 gap positions between them: the 32-position scale blocks then
 // fall at the same places inside an utterance, and no tile of one utterance reads a block of another, whatever else is in the
@@ -1018,6 +1062,8 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
     PK_DEVICE(ctx->device);
     const pk_wf_cfg& c = h->cfg;
     const int C = c.channels, M = c.n_mels, G = c.n_group, NL = c.n_layers, MP = h->mp, R = G - 1;
+    const int Z = 2 * h->dh_max;   // zero rows in front of the flat rows
+    static_assert(WFL_MAX_ROWS >= 128, "the by-value row maps hold the largest n_group pk_wf_create accepts");
     const long hop = wf_hop(c);
     constexpr int FGAP = 192, CHUNK = 256;
     // ---- per-utterance sizes
@@ -1045,7 +1091,7 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
         sumP += (long)R * nch[b];
     }
     const long npos_l = (pos + PK_GEMM_BM - 1) / PK_GEMM_BM * PK_GEMM_BM;
-    if (npos_l * R >= (1L << 31) - 4096 || sumA >= (1L << 31)) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_forward: %ld positions per row are too many for one call; split the batch", npos_l);
+    if (npos_l * (R + Z) >= (1L << 31) - 4096 || sumA >= (1L << 31)) PK_FAIL(PK_EUNSUPPORTED, "pk_wf_forward: %ld positions per row are too many for one call; split the batch", npos_l);
     const int npos = (int)pos, npos_alloc = (int)npos_l;
     const long pstride = (long)npos_alloc + 2 * WF_LEAD;
     const long nflat = (long)R * npos_alloc;        // positions of the flat rows of one flow
@@ -1117,9 +1163,9 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
     const bool use_wfl = wfl_usable(h) && (h->math == PK_GEMM_MATH_F16X3 || h->math == PK_GEMM_MATH_F16);
     const long cond_row = pstride * MP;                      // floats per folded cond row as the upsampler writes it
     const long frow = (long)npos_alloc * C;                  // floats per flat feature row
-    const size_t feat_bytes = ((size_t)(R + 2) * frow + 2 * (size_t)WF_LEAD * C) * 4;   // two zero rows + R rows + margins
+    const size_t feat_bytes = ((size_t)(R + Z) * frow + 2 * (size_t)WF_LEAD * C) * 4;   // Z zero rows + R rows + margins
     const size_t fcond_bytes = ((size_t)nflat + 2 * WF_LEAD) * MP * 4;
-    const long am_rows = (long)(R + 2) * nblk + 2 * (WF_LEAD / WFL_BLK);   // block maxima of one feature buffer incl. margins
+    const long am_rows = (long)(R + Z) * nblk + 2 * (WF_LEAD / WFL_BLK);   // block maxima of one feature buffer incl. margins
     PK_TRY(h->ws_cond.reserve((size_t)G * cond_row * 4));
     PK_TRY(h->ws_cur.reserve((size_t)G * pstride * 4));
     PK_TRY(h->ws_nxt.reserve((size_t)G * pstride * 4));
@@ -1194,8 +1240,8 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
             memset(&cm, 0, sizeof(cm));
             for (int r = 0; r < R; ++r) cm.row[r] = cidx[r + 1];
             PK_TRY(wfl_cond_planes_rows_launch(ctx, cond, cond_row, fcond, (long)npos_alloc * MP, fcam, nblk, cm, R, nblk, M));
-            // layer 0's input: input_proj of the rows 0 .. G-2 behind the two zero rows
-            PK_TRY(wfl_inproj_rows_launch(ctx, C, cur, pstride, h->W(F.w_in), h->W(F.b_in), fbuf[0] + 2 * frow, frow, fam[0] + 2 * nblk, nblk,
+            // layer 0's input: input_proj of the rows 0 .. G-2 behind the zero rows
+            PK_TRY(wfl_inproj_rows_launch(ctx, C, cur, pstride, h->W(F.w_in), h->W(F.b_in), fbuf[0] + Z * frow, frow, fam[0] + (long)Z * nblk, nblk,
                                           putt_flat, npos_alloc, R));
             for (int l = 0; l < NL; ++l) {
                 const WfLayerW& L = F.layers[l];
@@ -1204,15 +1250,15 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
                 memset(&w, 0, sizeof(w));
                 w.C = C;
                 w.f16 = h->math == PK_GEMM_MATH_F16;
-                w.slot_stride = frow;          // "ring slot" kr of a tile = the row kr - 2 rows before the tile's own
+                w.slot_stride = frow;          // "ring slot" s of a tile = the row Z - s rows before the tile's own
                 w.amax_stride = nblk;
-                w.cur_slot = 2;
+                w.cur_slot = Z;
                 w.prm = prm;
                 w.cond = fcond;
                 w.cond_amax = fcam;
                 w.ntap = 9;
                 for (int t = 0; t < 9; ++t) {
-                    w.tap_slot[t] = t / 3;
+                    w.tap_slot[t] = Z - (2 - t / 3) * h->dil_h[l];   // kernel row kr = t / 3: (2 - kr) dh_l rows back
                     w.tap_col[t] = t % 3 - 1;
                     w.tap_w[t] = t;
                 }
@@ -1228,8 +1274,8 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
                 w.l0.w.k2res = L.fl.k2res;
                 w.l0.in0 = fbuf[in];
                 w.l0.in_amax0 = fam[in];
-                w.l0.out = l + 1 < NL ? fbuf[out] + 2 * frow : nullptr;   // the last layer's residual output is unused (:390)
-                w.l0.out_amax = l + 1 < NL ? fam[out] + 2 * nblk : nullptr;
+                w.l0.out = l + 1 < NL ? fbuf[out] + Z * frow : nullptr;   // the last layer's residual output is unused (:390)
+                w.l0.out_amax = l + 1 < NL ? fam[out] + (long)Z * nblk : nullptr;
                 w.l0.first = l == 0;
                 w.l0.dil = 1 << l;
                 PK_TRY(wfl_layer_launch(ctx, w));
@@ -1244,11 +1290,11 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
                 PK_HIP(hipMemcpyAsync(fcond + (size_t)r * npos_alloc * MP, cond + (size_t)cidx[r + 1] * cond_row, (size_t)npos_alloc * MP * 4,
                                       hipMemcpyDeviceToDevice, ctx->stream));
             PK_LAUNCH(ctx, "wf_inproj_rows", k_wf_inproj_rows_f32, dim3(pk_div_up(nflat * C, 256)), dim3(256), 0, cur, pstride, h->W(F.w_in),
-                      h->W(F.b_in), fbuf[0] + 2 * frow, putt_flat, npos_alloc, nflat * C, C);
+                      h->W(F.b_in), fbuf[0] + Z * frow, putt_flat, npos_alloc, nflat * C, C);
             for (int l = 0; l < NL; ++l) {
                 const WfLayerW& L = F.layers[l];
-                float* in = fbuf[l & 1] + 2 * frow;    // row r of the layer input (rows r - 2, r - 1 in front of it)
-                float* out = fbuf[(l & 1) ^ 1] + 2 * frow;
+                float* in = fbuf[l & 1] + Z * frow;    // row r of the layer input (the rows before it, zero rows first, in front of it)
+                float* out = fbuf[(l & 1) ^ 1] + Z * frow;
                 pk_gemm_args g;
                 g.A = in;
                 g.lda = C;
@@ -1257,7 +1303,7 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
                 const long dil = 1L << l;
                 for (int kr = 0; kr < 3; ++kr)
                     for (int kc = 0; kc < 3; ++kc) {
-                        g.tap_off[g.ntaps] = (long)(kr - 2) * frow + (long)(kc - 1) * dil * C;
+                        g.tap_off[g.ntaps] = (long)(kr - 2) * h->dil_h[l] * frow + (long)(kc - 1) * dil * C;
                         g.tap_w[g.ntaps] = kr * 3 + kc;
                         ++g.ntaps;
                     }
