@@ -75,7 +75,34 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef PK_PWG_NT_XOUT
 #define PK_PWG_NT_XOUT 1
 #endif
+// The skip accumulator of the split kernels (k_pwg_layer_b3, k_pwg_last_h3) in accumulator order.  A lane (j = lane & 31, hi = lane >> 5) holds in
+// accumulator registers 4 r4 .. 4 r4 + 3 of output tile q the four consecutive channels 32 q + 8 r4 + 4 hi + {0..3} of sample j (mfma_row), so with a
+// 32-sample block laid out [channel quad c4 = ch >> 2 (16)][sample 32][4 channels] (the same 8 KB) those four registers are ONE aligned 16-byte vector at
+// c4 = 8 q + 2 r4 + hi, and a wave instruction covers 1 KB of contiguous memory: 8 + 8 16-byte accesses per tile instead of 32 + 32 dword accesses of two
+// 128-byte segments each, i.e. 16 instead of 64 entries of the in-order vmcnt queue the next tile's operand ring drains behind.  A permutation of where
+// values live: every value and every operation stays as it was.  0 = [channel 64][sample 32] and dword accesses (the A/B: profiles/pwg_skip_vec_ab.txt).
+// The exact-fp32 kernels (k_pwg_layer, k_pwg_last) keep [channel][sample]; a call runs one family or the other, never both (pk_pwg::last_skip_vec).
+#ifndef PK_PWG_SKIP_VEC
+#define PK_PWG_SKIP_VEC 1
+#endif
+#if PK_PWG_SKIP_VEC && PK_PWG_SKIP_SCOPE != 0
+#error "PK_PWG_SKIP_SCOPE measures the dword skip stream: build it with PK_PWG_SKIP_VEC=0"
+#endif
 namespace {
+__device__ __forceinline__ f32x4 pwg_skip_ld4(const float* p) {
+#if PK_PWG_NT_SKIP
+    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+#else
+    return *reinterpret_cast<const f32x4*>(p);
+#endif
+}
+__device__ __forceinline__ void pwg_skip_st4(f32x4 v, float* p) {
+#if PK_PWG_NT_SKIP
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
+#else
+    *reinterpret_cast<f32x4*>(p) = v;
+#endif
+}
 __device__ __forceinline__ float pwg_skip_ld(const float* p) {
 #if PK_PWG_SKIP_SCOPE == 1
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -384,7 +411,7 @@ __global__ void k_pwg_aux_debug(const float* __restrict__ P, int ldp, int col0, 
 struct PwgLayerArgs {
     const float* xin;     // [R][Ttot]
     float* xout;          // [R][Ttot]
-    float* skip;          // [SK][Ttot]
+    float* skip;          // [SK][Ttot], blocked like x; k_pwg_layer_b3 under PK_PWG_SKIP_VEC: every block in accumulator order [ch >> 2][sample][ch & 3]
     const float* w1;      // [KS1][64 lanes][4 co-tiles]  A fragments, dilated conv
     const float* w2;      // [KS2][64 lanes][4 out-tiles] A fragments, out / skip 1x1 convs
     const float* bias;    // [G + R + SK]: conv bias (gate), conv1x1_out bias, conv1x1_skip bias
@@ -875,6 +902,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
     int my_slot = wg_slot * LAYER_WAVES + wave;
 #if PK_PWG_TILE_MAP
     // which wave of the XCD's window of 8 * per_xcd wave tiles takes which tile (PK_PWG_TILE_MAP above)
+    static_assert(LAYER_WAVES == 8, "the tile maps below split a workgroup into waves 0..3 / 4..7 (wave >> 2, wave & 3) and the window into 8 per workgroup");
     if ((gridDim.x & 7) == 0) {
         const int wgl = (int)(blockIdx.x >> 3), win = per_xcd * LAYER_WAVES;
         const int local = PK_PWG_TILE_MAP == 1 ? (wave >> 2) * (win >> 1) + wgl * 4 + (wave & 3)      // first / second wave of the SIMDs: halves
@@ -1045,6 +1073,8 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
     // hold groups g+1..g+RING-1 (of this tile, continuing into the next one); slot g % RING is free.
     int amax_utt = -1;        // PL + AMAX: the utterance of the running maximum (wave-uniform) ...
     unsigned amax_run = 0u;   // ... and its bits
+    // (the tile loop must contain NO workgroup barrier: the waves of a workgroup take different numbers of tiles -- my_slot is per wave, and under
+    // PK_PWG_TILE_MAP a workgroup's waves sit in different halves of the window --, so a __syncthreads in here deadlocks on the last sweep)
     for (int wt = my_slot; wt < n_wtiles; wt += stride_slots) {
         const int next_wt = wt + stride_slots < n_wtiles ? wt + stride_slots : wt;
         unsigned vo8[3], pvo8[3];
@@ -1064,6 +1094,11 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         }
         int cls_next = 0;
         const unsigned vo4 = vo8[1];   // centre tap: operand rows and result rows share the lane offset
+#if PK_PWG_SKIP_VEC
+        // the lane's vector of channel quad hi in the tile's skip block (PK_PWG_SKIP_VEC above): + 128 floats per channel quad.  (vo4 = block * 2048
+        // + j + 128 hi: the tile is one whole block, its samples are the block's 0..31)
+        const unsigned svo = (vo4 & ~(unsigned)(XBLK_FLOATS - 1)) + (unsigned)(128 * hi + 4 * j);
+#endif
         float x_old[32];
         float nz_cur[3] = {0.f, 0.f, 0.f};
         if constexpr (NZ) {
@@ -1281,12 +1316,25 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
             for (int idx = 0; idx < 2 * B3_KS2; ++idx) {
                 const int ks = idx >> 1, q = idx & 1;
                 if (!FIRST && pass == 0 && idx == B3_KS2) {   // half of acc[] is dead by now: registers are free
+#if PK_PWG_SKIP_VEC
+#pragma unroll
+                    for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+                        for (int r4 = 0; r4 < 4; ++r4) {
+                            const f32x4 t = (ABL & 1) ? f32x4{0.5f, 0.5f, 0.5f, 0.5f} : pwg_skip_ld4((a.skip + (8 * qq + 2 * r4) * 128) + svo);
+                            sk_old[16 * qq + 4 * r4 + 0] = t[0];
+                            sk_old[16 * qq + 4 * r4 + 1] = t[1];
+                            sk_old[16 * qq + 4 * r4 + 2] = t[2];
+                            sk_old[16 * qq + 4 * r4 + 3] = t[3];
+                        }
+#else
 #pragma unroll
                     for (int qq = 0; qq < 2; ++qq)
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
                             sk_old[16 * qq + r] = (ABL & 1) ? 0.5f
                                                             : pwg_skip_ld((a.skip + (long)(32 * qq + mfma_row(r, 0)) * XBLK) + vo4);
+#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 // W2 fragments of the next (pass, ks, q) in issue order
@@ -1348,6 +1396,17 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
                         else v = FIRST ? acc2[q][r] : (sk_old[16 * q + r] + acc2[q][r]);
                         if (GEN && pass == 0 && !lane_valid) v = 0.f;
                     }
+#if PK_PWG_SKIP_VEC
+                    if (pass == 1) {   // the skip sum: registers 4 r4 .. 4 r4 + 3 leave as one vector
+                        acc2[q][r] = v;
+                        if ((r & 3) == 3) {
+                            const f32x4 v4 = {acc2[q][r - 3], acc2[q][r - 2], acc2[q][r - 1], acc2[q][r]};
+                            float* sp = (dst + (8 * q + 2 * (r >> 2)) * 128) + svo;
+                            if constexpr (PL) pwg_skip_st4(v4, sp);
+                            else if (!(ABL & 1) || a.Ttot < 0) *reinterpret_cast<f32x4*>(sp) = v4;
+                        }
+                    } else
+#endif
                     if constexpr (PL) {
                         if (pass == 0) acc2[q][r] = v;   // stored below, once the block's maximum (its scale) is known
                         else pwg_skip_st(v, (dst + (long)(32 * q + mfma_row(r, 0)) * XBLK) + vo4);
@@ -1412,7 +1471,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
 // last_conv_layers: ReLU -> Conv1D(SK->SK,1) -> ReLU -> Conv1D(SK->1,1) (:429-440,471) on
 // skips * sqrt(1/layers) (:469).  One workgroup per tile, 8 waves x 32 samples.
 struct PwgLastArgs {
-    const float* skip;   // [SK][Ttot]
+    const float* skip;   // [SK][Ttot], blocked; k_pwg_last_h3 under PK_PWG_SKIP_VEC: every block in accumulator order, as k_pwg_layer_b3 left it
     const float* w1;     // [SK/2 k-steps][64 lanes][2 co-tiles] A fragments
     const float* b1;     // [SK]
     const float* w2;     // [SK]
@@ -1489,14 +1548,31 @@ __global__ __launch_bounds__(512) void k_pwg_last_h3(PwgLastArgs a) {
     const int hi = lane >> 5;
     const int tile = blockIdx.x;
     const long t = (long)(a.tile_t0[tile] & ~255) + wave * WAVE_T + j;
-    const float* sb = a.skip + xoff(t) + 4 * hi * XBLK;
     float sv[4][8];
+#if PK_PWG_SKIP_VEC
+    // accumulator order (PK_PWG_SKIP_VEC above): elements 4 eh .. 4 eh + 3 of k-step ks are accumulator registers 4 r4 .. 4 r4 + 3 of tile q = ks >> 1 with
+    // r4 = 2 (ks & 1) + eh, i.e. the lane's vector of channel quad 8 q + 2 r4 + hi
+    const f32x4* sb = reinterpret_cast<const f32x4*>(a.skip + (t >> 5) * XBLK_FLOATS + 128 * hi + 4 * j);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int eh = 0; eh < 2; ++eh) {
+            const int c4 = 8 * (ks >> 1) + 2 * (2 * (ks & 1) + eh);
+            const f32x4 v4 = PK_PWG_NT_EDGE ? __builtin_nontemporal_load(sb + c4 * 32) : sb[c4 * 32];
+            sv[ks][4 * eh + 0] = v4[0];
+            sv[ks][4 * eh + 1] = v4[1];
+            sv[ks][4 * eh + 2] = v4[2];
+            sv[ks][4 * eh + 3] = v4[3];
+        }
+#else
+    const float* sb = a.skip + xoff(t) + 4 * hi * XBLK;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             sv[ks][e] = PK_PWG_NT_EDGE ? __builtin_nontemporal_load(sb + (long)(32 * (ks >> 1) + mfma_row(8 * (ks & 1) + e, 0)) * XBLK)
                                        : sb[(long)(32 * (ks >> 1) + mfma_row(8 * (ks & 1) + e, 0)) * XBLK];
+#endif
     f32x16 acc[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q)
@@ -1589,6 +1665,7 @@ struct pk_pwg {
     int dbg = 0;
     bool planes_on = true;     // x as pre-split fp16 planes under the split-fp16 math (k_pwg_layer_b3<..., PL>); PK_PWG_PLANES=0: off
     bool last_planes = false;  // ... and whether the last run used them (debug tap 1 decodes)
+    bool last_skip_vec = false;   // the last run left the skip sum in accumulator order (PK_PWG_SKIP_VEC: the split kernels; debug tap 2 decodes)
     // "scale_guard": 0 off, 1 the first inference after finalize, 2 every inference.  A guarded inference on the planes path
     // measures max|x| per utterance and layer (k_pwg_planes_amax) and compares with the a-priori bound of k_pwg_tile_scales
     int scale_guard = 1;
@@ -2162,7 +2239,7 @@ extern "C" int pk_pwg_finalize(pk_pwg* h) {
     // The deferred scale-guard sample's landing place and its event are created HERE (hipHostMalloc and
     // hipEventCreate synchronise the device and are illegal under stream capture -- they used to run inside the 16th
     // pk_pwg_infer).  Sized for PWG_SAMPLE_MAX_B utterances (0.5 MB pinned); a sampled call with more utterances than that is
-    // not sampled (samples_skipped counts them; "scale_guard" 2 guards every call regardless of size).
+    // not sampled (samples_dropped counts them; "scale_guard" 2 guards every call regardless of size).
     if (!h->host_sample) {
         const size_t need = (size_t)(c.layers + 2) * PWG_SAMPLE_MAX_B * sizeof(float);
         PK_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_sample), need, hipHostMallocDefault));
@@ -2410,6 +2487,7 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
     for (int attempt = 0;; ++attempt) {
     bool amax_parts_used = false;   // AMAX layer kernels ran: their parts are folded into amax[] behind the stack
     h->last_planes = planes;
+    h->last_skip_vec = PK_PWG_SKIP_VEC != 0 && h->math != PK_PWG_MATH_F32;   // every k_pwg_layer_b3 + k_pwg_last_h3, planes or not: an attempt writes the whole sum
     int* tkx = nullptr;
     if (planes) {
         PK_TRY(h->ws_nmax.reserve((size_t)B * 4));
@@ -2684,6 +2762,17 @@ extern "C" int pk_pwg_debug_read(pk_pwg* h, int32_t what, int32_t b, float* host
                     host_out[(size_t)ch * S + bi * XBLK + sidx] = (float)(((double)f16_to_f32(v[e]) + (double)f16_to_f32(v[8 + e])) * inv);
                 }
         }
+        return PK_OK;
+    }
+    if (what == 2 && h->last_skip_vec) {
+        // the skip sum in accumulator order: whole blocks to the host, decoded there -- [channel quad 16][sample 32][4 channels] per block
+        const long nblk = (S + XBLK - 1) / XBLK, blk0 = h->last_toff[b] / XBLK;
+        std::vector<float> raw((size_t)nblk * XBLK_FLOATS);
+        PK_HIP(hipMemcpy(raw.data(), src + (size_t)blk0 * XBLK_FLOATS, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (long bi = 0; bi < nblk; ++bi)
+            for (int ch = 0; ch < SK; ++ch)
+                for (int sidx = 0; sidx < XBLK && bi * XBLK + sidx < S; ++sidx)
+                    host_out[(size_t)ch * S + bi * XBLK + sidx] = raw[(size_t)bi * XBLK_FLOATS + (size_t)(ch >> 2) * (4 * XBLK) + sidx * 4 + (ch & 3)];
         return PK_OK;
     }
     // blocked layout: channel ch of this utterance = S/32 pieces of 32 floats, one per block (+ a shorter last

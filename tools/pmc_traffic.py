@@ -4,7 +4,8 @@ usage: pmc_traffic.py pwg|wf <pmc json of tools/pmc_parse.py> <out json>
 Counter handling as MI355X_MICROARCH.md's HBM section prescribes: FETCH_SIZE / WRITE_SIZE are KB of L2 <-> fabric requests
 (Infinity Cache hits included); on gfx950 FETCH_SIZE reports half the bytes of wide coalesced reads, other patterns are
 uncalibrated -- so every factor is taken from a kernel of the same run whose byte count is known exactly:
-  pwg:  reads  k_pwg_last[_h3]   (64 ch x 4 B per sample, dword per lane -- the layer kernel's pattern)
+  pwg:  reads  k_pwg_last[_h3]   (64 ch x 4 B per sample, in the layer kernel's own access shape: 16 B per lane of the skip sum in accumulator
+                                  order (pwg.hip, PK_PWG_SKIP_VEC), a dword per lane and two 128-B segments per instruction before that)
         writes k_pwg_first       (64 ch x 4 B per sample); without it (noise-fed first block) the first block's own launch (2 x 64 ch x 4 B)
   wf:   reads  the guide's factor 2 (16 B per lane, the layer kernel's only access width), cross-checked on
                k_wf_cond_planes (reads and rewrites 96 x 32 x 4 B per block)
@@ -34,8 +35,8 @@ if kind == "pwg":
     targs = [t.strip() for t in LK[LK.index("<") + 1:LK.rindex(">")].split(",")]   # <FIRST, HALF[, ABL]>
     prof_key = ("pwg_layer_h3" if targs[1] == "true" else "pwg_layer_b3") if "b3" in LK else "pwg_layer"
     extra = {"prof_key": prof_key, "samples_per_launch": n,
-             "calibration_note": "FETCH_SIZE calibrated on k_pwg_last[_h3] (reads exactly 64x4 B/sample with the same dword-per-lane, "
-                                 "128-B-segment pattern), WRITE_SIZE on k_pwg_first (writes exactly 64x4 B/sample) or, without it, on the noise-fed first block (2x64x4 B/sample); "
+             "calibration_note": "FETCH_SIZE calibrated on k_pwg_last[_h3] (reads exactly 64x4 B/sample in the access shape of the layer "
+                                 "kernel's skip read), WRITE_SIZE on k_pwg_first (writes exactly 64x4 B/sample) or, without it, on the noise-fed first block (2x64x4 B/sample); "
                                  "MI355X_MICROARCH.md HBM section: FETCH_SIZE under-counts wide streams by 2x on gfx950"}
 else:
     LK = [k for k in d if k.startswith("k_wf_layer_p<2, 3, 0")][0]
