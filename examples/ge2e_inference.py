@@ -8,8 +8,9 @@ embedding, the conditions Tacotron2-aishell3 is trained on.  As in the reference
 engine in batches of ``--batch`` utterances, each ONE ``embed_utterances`` call (the reference embeds file by file).
 
 ``--config`` is a YAML file with ``data`` / ``model`` sections overriding examples/ge2e/config.py's defaults; ``--opts``
-takes ``KEY VALUE`` pairs such as ``data.n_mels 40``.  Files: 16-bit PCM WAV; other rates are resampled with
-scipy.signal.resample_poly (not librosa's resampler).  Silence trimming is skipped (no webrtcvad), as the reference
+takes ``KEY VALUE`` pairs such as ``data.n_mels 40``.  Files: PCM or float WAV; other rates are resampled with
+scipy.signal.resample_poly on the host (``--resampler scipy``, the default) or by the engine's polyphase kernel
+(``--resampler engine``); neither is librosa's resampler.  Silence trimming is skipped (no webrtcvad), as the reference
 does without that package.
 """
 import argparse
@@ -62,6 +63,7 @@ def main():
     ap.add_argument("--checkpoint_path", type=str, required=True, help="checkpoint path without .pdparams")
     ap.add_argument("--device", type=str, choices=["cpu", "gpu"], default="gpu", help="ignored: the engine is the GPU")
     ap.add_argument("--batch", type=int, default=1024, help="utterances per engine call")
+    ap.add_argument("--resampler", choices=["scipy", "engine"], default="scipy", help="what resamples files at other rates")
     ap.add_argument("--opts", nargs=argparse.REMAINDER, help="KEY VALUE pairs overriding --config and the defaults")
     args = ap.parse_args()
     cfg = load_config(args.config, args.opts)
@@ -74,7 +76,8 @@ def main():
         vad_window_length=c["vad_window_length"], vad_moving_average_width=c["vad_moving_average_width"],
         vad_max_silence_length=c["vad_max_silence_length"], mel_window_length=c["mel_window_length"],
         mel_window_step=c["mel_window_step"], n_mels=c["n_mels"], partial_n_frames=c["partial_n_frames"],
-        min_pad_coverage=c["min_pad_coverage"], partial_overlap_ratio=c["min_pad_coverage"])   # sic: inference.py:81
+        min_pad_coverage=c["min_pad_coverage"], partial_overlap_ratio=c["min_pad_coverage"],   # sic: inference.py:81
+        resampler=args.resampler)
     input_dir = Path(args.input).expanduser()
     output_dir = Path(args.output).expanduser()
     ifpaths = sorted(input_dir.rglob(args.pattern))

@@ -1,9 +1,10 @@
 """Score vocoder output against the recordings with the multi-resolution STFT loss of the Parallel WaveGAN recipes: for every
-<utt_id>.wav in --gen-dir with a <utt_id>.wav in --ref-dir (16-bit PCM, same rate) print the utterance id, the samples
+<utt_id>.wav in --gen-dir with a <utt_id>.wav in --ref-dir (PCM or float, any rate) print the utterance id, the samples
 scored, the spectral convergence loss and the log STFT magnitude loss (each the mean over the resolutions), then the corpus
 means of the two -- what the reference's evaluator reports as eval/spectral_convergence_loss and
 eval/log_stft_magnitude_loss when it scores one utterance per batch.  A pair of unequal length is trimmed to the shorter one,
-and the line says so.
+and the line says so.  A pair is scored at the recording's rate: generated audio at another rate is resampled to it on the
+engine (parakeet_amd.audio.load_wav), and the line says so.
 
 With --discriminator-checkpoint (a snapshot_iter_*.pdz, which carries discriminator_params beside generator_params; needs
 --config for the discriminator's shape) every line gains four columns from the recipe's discriminator: the mean logit of the
@@ -20,7 +21,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from parakeet_amd.ge2e_audio import read_wav  # noqa: E402
+from parakeet_amd.audio import load_wav  # noqa: E402
 from parakeet_amd.stft_loss import MultiResolutionSTFTLoss  # noqa: E402
 
 
@@ -54,14 +55,16 @@ def main():
     for i in range(0, len(ids), a.batch):
         xs, ys, kept, notes = [], [], [], []
         for u in ids[i:i + a.batch]:
-            (x, sx), (y, sy) = read_wav(os.path.join(a.gen_dir, u + ".wav")), read_wav(os.path.join(a.ref_dir, u + ".wav"))
+            (x, sx), (y, sy) = load_wav(os.path.join(a.gen_dir, u + ".wav")), load_wav(os.path.join(a.ref_dir, u + ".wav"))
+            rnote = ""
             if sx != sy:
-                raise SystemExit(f"{u}: generated at {sx} Hz, recording at {sy} Hz")
+                rnote = f"\tresampled from {sx} Hz to {sy} Hz"
+                x = load_wav(os.path.join(a.gen_dir, u + ".wav"), sr=sy)[0]
             n = min(len(x), len(y))
             if n < need:
                 print(f"{u}\tskipped: {n} samples, the largest transform needs {need}", file=sys.stderr)
                 continue
-            notes.append("" if len(x) == len(y) else f"\ttrimmed from {len(x)} / {len(y)}")
+            notes.append(("" if len(x) == len(y) else f"\ttrimmed from {len(x)} / {len(y)}") + rnote)
             xs.append(x[:n])
             ys.append(y[:n])
             kept.append(u)

@@ -761,6 +761,38 @@ int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int32_t* frames
 int pk_gl_debug_read(pk_istft* h, int32_t what, float* out, int64_t n);
 void pk_istft_destroy(pk_istft* h);
 
+/* ------------------------------------------------------------- resampling */
+/* Rational-ratio resampling of ragged batches as a polyphase FIR (csrc/resample.hip); the reference's recipes begin with
+ * librosa.load(path, sr=fs) (examples/fastspeech2/preprocess.py:54-55), whose filter this is NOT: the filter is whatever
+ * table the caller passes (parakeet_amd/audio.py resample_filter builds a Kaiser-windowed sinc).
+ *   y[n] = sum_k table[(n * down) mod up][k] * x[floor(n * down / up) - (taps - 1) / 2 + k],   n = 0 ... ceil(N * up / down) - 1
+ * with x = 0 outside 0 ... N - 1: row p of `table` is the phase p / up, and tap k of a row multiplies the input sample
+ * k - (taps - 1) / 2 (integer division) away from the output's input base.  Taps are accumulated in ascending k with one fp32
+ * FMA each (the kernel also adds 0 * x for up to ceil(down / up) samples on either side of an output's taps: nothing for
+ * finite x, but an Inf or NaN sample reaches outputs that far beyond the filter's support too).  up = down = 1 is a plain FIR filter with the one row of the table (a caller that wants equal rates to be the
+ * identity does not call the engine: parakeet_amd.audio.Resample).
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): 1 <= up, down <= 4096; 1 <= taps <= 8192;
+ * up * taps <= 4 Mi coefficients. */
+typedef struct pk_resample pk_resample;
+typedef struct {
+    int32_t up;           /* L: target rate / gcd */
+    int32_t down;         /* M: source rate / gcd */
+    int32_t taps;         /* T: taps per phase */
+} pk_resample_cfg;
+/* table: HOST, (up, taps) row-major, copied. */
+int pk_resample_create(pk_ctx* ctx, const pk_resample_cfg* cfg, const float* table, pk_resample** out);
+/* n_out = ceil(n_in * up / down), 0 <= n_in < 2^31 (else PK_EINVAL). */
+int pk_resample_out_len(pk_resample* h, int64_t n_in, int64_t* n_out);
+/* Outputs per workgroup.  Tiles start at utterance-relative multiples of it (a multiple of up). */
+int pk_resample_tile_samples(pk_resample* h, int32_t* tile);
+/* wav: packed samples of B utterances, lens (B, host) >= 1 each; out: packed, pk_resample_out_len floats per utterance.
+ * An utterance's output is bit-identical alone, in any batch and at any position in it; the samples of its neighbours in the
+ * packed buffer are never read.
+ * PK_EINVAL: NULL pointer, B <= 0, an empty utterance.
+ * flags: PK_HOST_IO if wav / out are host pointers (then synchronous). */
+int pk_resample_run(pk_resample* h, const float* wav, const int32_t* lens, int32_t B, float* out, int32_t flags);
+void pk_resample_destroy(pk_resample* h);
+
 /* ------------------------------------------- multi-resolution STFT distance */
 /* parakeet/modules/stft_loss.py: what MultiResolutionSTFTLoss (:163-219) needs of two signals, reduced on the device.
  * A handle holds R resolutions.  n_fft must be a multiple of 16 (else PK_EUNSUPPORTED); hop_length is ANY integer >= 1

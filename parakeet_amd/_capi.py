@@ -103,6 +103,10 @@ class IstftCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32)]
 
 
+class ResampleCfg(C.Structure):
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("taps", C.c_int32)]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -258,6 +262,11 @@ def _declare(lib):
         "pk_gl_run": (C.c_int, [vp, vp, f32p, i32p, i32, i32, C.c_float, C.POINTER(C.c_uint64), f32p, f32p, i32]),
         "pk_gl_debug_read": (C.c_int, [vp, i32, f32p, i64]),
         "pk_istft_destroy": (None, [vp]),
+        "pk_resample_create": (C.c_int, [vp, C.POINTER(ResampleCfg), f32p, C.POINTER(vp)]),
+        "pk_resample_out_len": (C.c_int, [vp, i64, i64p]),
+        "pk_resample_tile_samples": (C.c_int, [vp, i32p]),
+        "pk_resample_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_resample_destroy": (None, [vp]),
         "pk_stftd_create": (C.c_int, [vp, C.POINTER(StftdCfg), C.POINTER(StftdRes), f32p, C.POINTER(vp)]),
         "pk_stftd_num_frames": (C.c_int, [vp, i32, i32, i32p]),
         "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),

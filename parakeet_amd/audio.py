@@ -10,9 +10,15 @@ which the reference calls at audio.py:221 / get_feats.py:49-55.
 The way back -- ``ISTFT``, ``AudioProcessor.stft`` / ``istft`` / ``griffin_lim`` / ``mel_to_linear`` and the weight-free
 ``GriffinLim`` vocoder -- follows parakeet/audio/audio.py:75-93 (librosa's ``istft``) and ``librosa.griffinlim``; it runs in
 csrc/istft.hip.
+
+``resample_filter`` / ``Resample`` / ``resample`` / ``load_wav`` put audio of any rate on the model's rate: a polyphase
+Kaiser-windowed sinc defined in DESIGN.md 4.5d (this project's own filter; the reference calls ``librosa.load(path, sr=fs)``,
+whose resampler is not available here and is not reproduced), run by csrc/resample.hip.
 """
 import ctypes as C
 import math
+import struct
+from fractions import Fraction
 
 import numpy as np
 import scipy.signal
@@ -279,7 +285,10 @@ class LogMelFBank:
                                       10 if base == "10" else 2)
         return self._eng[base]
 
-    def get_log_mel_fbank(self, wav, base="10"):
+    def get_log_mel_fbank(self, wav, base="10", sr=None):
+        """``sr``: the rate ``wav`` is at, when it is not the extractor's: it is resampled on the engine first."""
+        if sr is not None and int(sr) != int(self.sr):
+            wav = _resampler(sr, self.sr)(wav)
         return wrap(self._engine(base).run([wav], 2)[0])
 
     def get_log_mel_fbank_batch(self, wavs, base="10"):
@@ -339,26 +348,262 @@ class Energy:
             energy = wrap(average_by_duration(energy, duration).reshape(-1, 1))
         return energy
 
+# ---- resampling ------------------------------------------------------------------------------------------------------
+# name -> (zeros, rolloff, beta): the number of zero crossings kept on each side (at the lower of the two rates), the cutoff as
+# a fraction of the lower Nyquist frequency, the Kaiser window's beta.  DESIGN.md 4.5d.
+RESAMPLE_FILTERS = {
+    "kaiser_best": (64, 0.9475937167399596, 14.769656459379492),
+    "kaiser_fast": (16, 0.85, 8.555504641634386),
+}
+# the engine's envelope (csrc/pk_resample.h)
+RESAMPLE_MAX_RATIO, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_TABLE = 4096, 8192, 4 << 20
 
-def wav_bytes(wav, samplerate, subtype="PCM_16"):
+
+def _filter_params(res_type, zeros, rolloff, beta):
+    if res_type not in RESAMPLE_FILTERS:
+        raise ValueError(f"resample: unknown res_type {res_type!r} (one of {sorted(RESAMPLE_FILTERS)})")
+    z, r, b = RESAMPLE_FILTERS[res_type]
+    zeros, rolloff, beta = (z if zeros is None else zeros, r if rolloff is None else float(rolloff),
+                            b if beta is None else float(beta))
+    if not zeros > 0 or not 0 < rolloff <= 1 or not beta >= 0:
+        raise ValueError(f"resample: zeros = {zeros}, rolloff = {rolloff}, beta = {beta}: need zeros > 0, 0 < rolloff <= 1, "
+                         "beta >= 0")
+    return zeros, rolloff, beta
+
+
+def resample_ratio(orig_sr, target_sr):
+    """(up, down) = target_sr / orig_sr in lowest terms."""
+    if int(orig_sr) != orig_sr or int(target_sr) != target_sr or orig_sr <= 0 or target_sr <= 0:
+        raise ValueError(f"resample: sampling rates must be positive integers, got {orig_sr} and {target_sr}")
+    fr = Fraction(int(target_sr), int(orig_sr))
+    return fr.numerator, fr.denominator
+
+
+def resample_taps(up, down, zeros):
+    """T: taps per phase.  |s tau| < zeros with s = min(1, up / down) admits the input offsets -H ... H - 1 around an output's
+    input base, H = ceil(zeros / s)."""
+    return 2 * int(math.ceil(zeros * max(up, down) / up))
+
+
+def _check_resample_envelope(up, down, taps):
+    if not (1 <= up <= RESAMPLE_MAX_RATIO and 1 <= down <= RESAMPLE_MAX_RATIO):
+        raise NotImplementedError(f"resample: the ratio {up} / {down} in lowest terms is outside the engine's envelope: both "
+                                  f"terms must be in 1 ... {RESAMPLE_MAX_RATIO}")
+    if taps > RESAMPLE_MAX_TAPS:
+        raise NotImplementedError(f"resample: {taps} taps per phase; the engine's limit is {RESAMPLE_MAX_TAPS}")
+    if up * taps > RESAMPLE_MAX_TABLE:
+        raise NotImplementedError(f"resample: a table of up * taps = {up * taps} coefficients; the engine's limit is "
+                                  f"{RESAMPLE_MAX_TABLE}")
+
+
+def resample_filter(up, down, res_type="kaiser_best", zeros=None, rolloff=None, beta=None):
+    """The phase table of DESIGN.md 4.5d, (up, T) float64, numpy only.
+
+    With s = min(1, up / down):  g(tau) = s rolloff sinc(rolloff s tau) K(s tau / zeros) for |s tau| < zeros, else 0;
+    K(u) = I0(beta sqrt(1 - u^2)) / I0(beta).  Row p, tap k is g(H - 1 - k + p / up), H = T / 2 = ceil(zeros / s): the weight of
+    the input sample k - (H - 1) away from the input base floor(n down / up) of an output n with (n down) mod up = p (the
+    layout of ``pk_resample_create``).  s tau is formed as an integer over max(up, down), so the support test is exact."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"resample_filter: up = {up}, down = {down} must be positive")
+    zeros, rolloff, beta = _filter_params(res_type, zeros, rolloff, beta)
+    T = resample_taps(up, down, zeros)
+    H = T // 2
+    q = (H - 1 - np.arange(T, dtype=np.int64))[None, :] * up + np.arange(up, dtype=np.int64)[:, None]   # tau = q / up
+    st = q.astype(np.float64) / float(max(up, down))                                                       # s tau
+    inside = np.abs(st) < zeros
+    u = np.where(inside, st / zeros, 0.0)
+    s = min(1.0, up / down)
+    g = s * rolloff * np.sinc(rolloff * st) * np.i0(beta * np.sqrt(1.0 - u * u)) / np.i0(beta)
+    return np.where(inside, g, 0.0)
+
+
+class Resample:
+    """``orig_sr`` -> ``target_sr`` on the engine (``pk_resample_*``): y[n] = sum_m x[m] g(n down / up - m) with the filter of
+    ``resample_filter``, ceil(N up / down) outputs, zeros outside the signal.  Equal rates return the input as it is (no
+    filter, no engine call).  Ragged batches run as one engine call; an utterance's result does not depend on its batch."""
+
+    def __init__(self, orig_sr, target_sr, res_type="kaiser_best", zeros=None, rolloff=None, beta=None, device=None):
+        self.orig_sr, self.target_sr = int(orig_sr), int(target_sr)
+        self.up, self.down = resample_ratio(orig_sr, target_sr)
+        self.zeros, self.rolloff, self.beta = _filter_params(res_type, zeros, rolloff, beta)
+        self._device = device
+        self.h = None
+        self.taps = 0
+        if self.up == 1 and self.down == 1:
+            return
+        self.taps = resample_taps(self.up, self.down, self.zeros)
+        _check_resample_envelope(self.up, self.down, self.taps)
+        self.ctx = Context.get(device)
+        self.table = np.ascontiguousarray(
+            resample_filter(self.up, self.down, res_type, self.zeros, self.rolloff, self.beta), dtype=np.float32)
+        cfg = _capi.ResampleCfg(self.up, self.down, self.taps)
+        h = C.c_void_p()
+        _capi.check(self.ctx.lib.pk_resample_create(self.ctx.handle, C.byref(cfg), _capi.fptr(self.table), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.ctx.lib.pk_resample_destroy(h)
+            except Exception:
+                pass
+
+    def output_length(self, n):
+        return -(-int(n) * self.up // self.down)
+
+    @property
+    def tile_samples(self):
+        """Outputs per workgroup of the engine's kernel (0 for equal rates)."""
+        if self.h is None:
+            return 0
+        t = C.c_int32()
+        _capi.check(self.ctx.lib.pk_resample_tile_samples(self.h, C.byref(t)))
+        return t.value
+
+    def run_batch(self, wavs):
+        """A list of 1-D signals (numpy or tensors) -> a list of (output_length,) device tensors, one engine call."""
+        ctx = Context.get(self._device)
+        xs = [ctx.to_device(w).reshape(-1) for w in wavs]
+        if self.h is None or not xs:
+            return [wrap(x) for x in xs]
+        lens = np.array([x.numel() for x in xs], dtype=np.int32)
+        if lens.min() < 1:
+            raise ValueError("Resample: an empty signal")
+        x = xs[0] if len(xs) == 1 else torch.cat(xs)
+        n_out = [self.output_length(n) for n in lens]
+        out = ctx.empty((sum(n_out),))
+        _capi.check(ctx.lib.pk_resample_run(self.h, dptr(x), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(xs), dptr(out), 0))
+        res, o = [], 0
+        for n in n_out:
+            res.append(wrap(out[o:o + n]))
+            o += n
+        return res
+
+    def __call__(self, wav):
+        return self.run_batch([wav])[0]
+
+
+_RESAMPLERS = {}
+
+
+def _resampler(orig_sr, target_sr, res_type="kaiser_best", zeros=None, rolloff=None, beta=None, device=None):
+    """One ``Resample`` per (ratio, filter, device): the table is built and uploaded once."""
+    up, down = resample_ratio(orig_sr, target_sr)
+    dev = torch.cuda.current_device() if device is None and torch.cuda.is_available() else device
+    key = (up, down, res_type, zeros, rolloff, beta, str(dev))
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = Resample(orig_sr, target_sr, res_type, zeros, rolloff, beta, device)
+    return _RESAMPLERS[key]
+
+
+def resample(y, orig_sr, target_sr, **kw):
+    """numpy in, numpy out (float32), on the engine; the argument order of ``librosa.resample``, NOT its filter (see
+    ``Resample``).  The last axis is time; leading axes are resampled as a batch.  Equal rates return the samples as they
+    are."""
+    y = np.asarray(y, dtype=np.float32)
+    if resample_ratio(orig_sr, target_sr) == (1, 1):
+        return y.copy()
+    rs = _resampler(orig_sr, target_sr, **kw)
+    if y.ndim == 1:
+        return rs(y).cpu().numpy()
+    rows = y.reshape(-1, y.shape[-1])
+    out = rs.run_batch(list(rows))
+    return torch.stack(out).cpu().numpy().reshape(y.shape[:-1] + (-1,))
+
+
+def _decode_wav(data):
+    """RIFF/WAVE bytes -> ((frames, channels) samples, rate, bits, is_float); integer PCM of 8, 16, 24, 32 bits, IEEE float32,
+    plain or WAVE_FORMAT_EXTENSIBLE."""
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError("not a RIFF/WAVE file")
+    pos, fmt, body = 12, None, None
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        chunk = data[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            fmt = chunk
+        elif cid == b"data":
+            body = chunk
+            break
+        pos += 8 + size + (size & 1)
+    if fmt is None or body is None or len(fmt) < 16:
+        raise ValueError("no fmt / data chunk")
+    tag, ch, rate, _, block, bits = struct.unpack("<HHIIHH", fmt[:16])
+    if tag == 0xFFFE and len(fmt) >= 26:
+        tag = struct.unpack("<H", fmt[24:26])[0]            # the sub-format GUID starts with the plain format tag
+    if ch < 1 or rate < 1:
+        raise ValueError(f"{ch} channels at {rate} Hz")
+    if (tag, bits) not in ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32)):
+        raise NotImplementedError(f"format tag {tag} with {bits} bits per sample (integer PCM of 8 / 16 / 24 / 32 bits and "
+                                  "32-bit float are read)")
+    width = bits // 8
+    body = body[:len(body) // (width * ch) * (width * ch)]
+    if tag == 3:
+        x = np.frombuffer(body, dtype="<f4")
+    elif bits == 8:
+        x = np.frombuffer(body, dtype=np.uint8).astype(np.int16) - 128
+    elif bits == 16:
+        x = np.frombuffer(body, dtype="<i2")
+    elif bits == 32:
+        x = np.frombuffer(body, dtype="<i4")
+    else:
+        b = np.frombuffer(body, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        x = (b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16))
+        x = x - ((x & 0x800000) << 1)
+    return x.reshape(-1, ch), rate, bits, tag == 3
+
+
+def load_wav(path, sr=None, mono=True, res_type="kaiser_best"):
+    """(float32 wav, sampling rate) of a RIFF/WAVE file: the ``librosa.load(path, sr=fs)`` the reference's feature recipes begin
+    with (examples/fastspeech2/preprocess.py:54-55), with this project's resampler in place of librosa's.  Integer samples are
+    divided by 2^(bits - 1); ``mono`` averages the channels, otherwise the result is (channels, T) for a file of several.
+    ``sr``: None keeps the file's rate; another rate resamples on the engine (``Resample``).  ``path`` may be bytes."""
+    if isinstance(path, (bytes, bytearray)):
+        data = bytes(path)
+    elif hasattr(path, "read"):
+        data = path.read()
+    else:
+        with open(path, "rb") as f:
+            data = f.read()
+    try:
+        x, rate, bits, is_float = _decode_wav(data)
+    except (ValueError, NotImplementedError) as e:
+        raise type(e)(f"{path if not isinstance(path, (bytes, bytearray)) else '<bytes>'}: {e}") from None
+    acc = np.float64 if bits == 32 and not is_float else np.float32       # 24 bits are exact in float32, 32 are not
+    x = x.astype(acc)
+    x = x.mean(axis=1) if mono or x.shape[1] == 1 else np.ascontiguousarray(x.T)
+    if not is_float:
+        x = x / acc(1 << (bits - 1))
+    wav = x.astype(np.float32, copy=False)
+    if sr is not None and int(sr) != rate:
+        wav = resample(wav, rate, sr, res_type=res_type)
+        rate = int(sr)
+    return wav, rate
+
+
+def wav_bytes(wav, samplerate, subtype="PCM_16", source_samplerate=None):
     """The bytes ``write_wav`` puts into the file (a serving process sends them instead of writing a file)."""
     import io
     buf = io.BytesIO()
-    write_wav(buf, wav, samplerate, subtype)
+    write_wav(buf, wav, samplerate, subtype, source_samplerate)
     return buf.getvalue()
 
 
-def write_wav(path, wav, samplerate, subtype="PCM_16"):
+def write_wav(path, wav, samplerate, subtype="PCM_16", source_samplerate=None):
     """Minimal stand-in for the ``soundfile.write(path, wav.numpy(), samplerate=fs)`` at the end of the
     synthesis recipes (examples/fastspeech2/ljspeech/synthesize_e2e.py:104-107): RIFF/WAVE, mono or
     (T, C) float input in [-1, 1].  "PCM_16" (libsndfile's default for .wav: clip, scale by 32767, round to
-    nearest) or "FLOAT" (32-bit IEEE samples, lossless)."""
-    import struct
+    nearest) or "FLOAT" (32-bit IEEE samples, lossless).  ``source_samplerate``: the rate ``wav`` is at, when the file is to
+    be at another one (``samplerate``): it is resampled on the engine (``Resample``) before it is encoded."""
     x = np.asarray(wav.cpu() if isinstance(wav, torch.Tensor) else wav, dtype=np.float32)
     if x.ndim == 1:
         x = x[:, None]
     if x.ndim != 2:
         raise ValueError("write_wav: expected (T,) or (T, channels)")
+    if source_samplerate is not None and int(source_samplerate) != int(samplerate):
+        x = np.ascontiguousarray(resample(np.ascontiguousarray(x.T), source_samplerate, samplerate).T)
     n, ch = x.shape
     if subtype == "PCM_16":
         data = np.rint(np.clip(x, -1.0, 1.0) * 32767.0).astype("<i2").tobytes()
@@ -423,8 +668,8 @@ class UnitMagnitude:
 class AudioProcessor:
     """parakeet/audio/audio.py:20-102 with the transforms on the engine: ``spectrogram`` = |STFT|,
     ``mel_spectrogram`` = mel_filter . |STFT| (the Slaney filterbank of ``librosa.filters.mel``), both returned
-    as (bins, frames) numpy arrays like the reference.  ``read_wav`` reads PCM / float RIFF files at the
-    processor's sample rate (the reference resamples with librosa, which this image does not have)."""
+    as (bins, frames) numpy arrays like the reference.  ``read_wav`` reads PCM / float RIFF files (``load_wav``); a file at
+    another rate is resampled to the processor's on the engine, where the reference resamples with librosa."""
 
     def __init__(self, sample_rate, n_fft, win_length, hop_length, n_mels=80, fmin=0, fmax=None, window="hann",
                  center=True, pad_mode="reflect", normalize=True):
@@ -441,16 +686,7 @@ class AudioProcessor:
         self._inv = None
 
     def read_wav(self, filename):
-        import wave
-        with wave.open(str(filename), "rb") as w:
-            if w.getframerate() != self.sample_rate:
-                raise NotImplementedError(f"{filename}: {w.getframerate()} Hz, resampling to {self.sample_rate} Hz "
-                                          "needs librosa")
-            raw = w.readframes(w.getnframes())
-            ch, width = w.getnchannels(), w.getsampwidth()
-        if width != 2:
-            raise NotImplementedError("read_wav: 16-bit PCM only")
-        wav = np.frombuffer(raw, dtype="<i2").astype(np.float32).reshape(-1, ch).mean(axis=1) / 32768.0
+        wav, _ = load_wav(filename, sr=self.sample_rate)
         if self.normalize:
             wav = wav / np.max(np.abs(wav)) * 0.999
         return wav

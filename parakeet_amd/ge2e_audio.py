@@ -8,7 +8,8 @@ partial batches stay on the device.
 Differences from the reference, both forced by what this package depends on:
   * silence trimming needs ``webrtcvad``; without it the reference skips the step with a warning (:23-27, :217-220),
     and so does this module, always (one warning per process);
-  * other sampling rates are resampled with ``scipy.signal.resample_poly``, which is not librosa's resampler.
+  * other sampling rates are resampled with ``scipy.signal.resample_poly`` on the host (``resampler="scipy"``, the default)
+    or with the engine's polyphase kernel (``resampler="engine"``, ``audio.Resample``); neither is librosa's resampler.
 """
 import warnings
 from fractions import Fraction
@@ -16,7 +17,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from .audio import _Engine, mel_filterbank
+from .audio import _Engine, _resampler, load_wav, mel_filterbank
 
 _VAD_WARNED = False
 
@@ -83,7 +84,10 @@ def resample(wav, source_sr, target_sr):
 class SpeakerVerificationPreprocessor:
     def __init__(self, sampling_rate, audio_norm_target_dBFS, vad_window_length, vad_moving_average_width,
                  vad_max_silence_length, mel_window_length, mel_window_step, n_mels, partial_n_frames,
-                 min_pad_coverage=0.75, partial_overlap_ratio=0.5, device=None):
+                 min_pad_coverage=0.75, partial_overlap_ratio=0.5, device=None, resampler="scipy"):
+        if resampler not in ("scipy", "engine"):
+            raise ValueError(f"resampler must be 'scipy' or 'engine', got {resampler!r}")
+        self.resampler = resampler
         self.sampling_rate = sampling_rate
         self.audio_norm_target_dBFS = audio_norm_target_dBFS
         self.vad_window_length = vad_window_length
@@ -106,11 +110,14 @@ class SpeakerVerificationPreprocessor:
 
     def preprocess_wav(self, fpath_or_wav, source_sr=None):
         if isinstance(fpath_or_wav, (str, bytes)) or hasattr(fpath_or_wav, "__fspath__"):
-            wav, source_sr = read_wav(fpath_or_wav)
+            wav, source_sr = load_wav(fpath_or_wav)
         else:
             wav = np.asarray(fpath_or_wav, dtype=np.float32)
         if source_sr is not None and source_sr != self.sampling_rate:
-            wav = resample(wav, source_sr, self.sampling_rate)
+            if self.resampler == "engine":
+                wav = _resampler(source_sr, self.sampling_rate, device=self._device)(wav).cpu().numpy()
+            else:
+                wav = resample(wav, source_sr, self.sampling_rate)
         wav = normalize_volume(wav, self.audio_norm_target_dBFS, increase_only=True)
         _warn_no_vad()
         return wav
@@ -144,9 +151,9 @@ class SpeakerVerificationPreprocessor:
         return out
 
 
-def ge2e_preprocessor(overlap=0.5, device=None):
+def ge2e_preprocessor(overlap=0.5, device=None, resampler="scipy"):
     """The released configuration (examples/ge2e/config.py): 16 kHz, -30 dBFS, 25 ms / 10 ms windows, 40 mels,
     160-frame partials, min_pad_coverage 0.75.  examples/ge2e/inference.py passes ``partial_overlap_ratio =
     min_pad_coverage`` (:81): use overlap=0.75 to reproduce its corpus embeddings; the class default is 0.5."""
     return SpeakerVerificationPreprocessor(16000, -30, 30, 8, 6, 25, 10, 40, 160, min_pad_coverage=0.75,
-                                           partial_overlap_ratio=overlap, device=device)
+                                           partial_overlap_ratio=overlap, device=device, resampler=resampler)

@@ -22,7 +22,7 @@ OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libpk_synth_emu.so")
 CXX = os.environ.get("HIPEMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 
-_DYN_LDS = re.compile(r"extern\s+__shared__\s+(\w+)\s+(\w+)\[\];")
+_DYN_LDS = re.compile(r"extern\s+__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?(\w+)\s+(\w+)\[\];")
 _WAVE_LDS = re.compile(r"^(\s*)// \[wave-lds-exchange\]", re.M)
 _STATIC_LDS = re.compile(r"^(\s*)(__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?[\w:<>]+\s+(\w+)(?:\[[^\];]+\])+;)", re.M)
 _FMA_MIX = re.compile(r'asm\("v_fma_mix_f32 %0, %1, -1\.0, %2 op_sel:\[(\d),0,0\] op_sel_hi:\[1,0,0\]"\s*:\s*"=v"\((\w+)\)\s*:\s*'

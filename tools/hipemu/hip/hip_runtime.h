@@ -279,6 +279,7 @@ static inline float __uint_as_float(unsigned i) { float f; std::memcpy(&f, &i, 4
 static inline unsigned __umulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
 static inline float rsqrtf(float x) { return 1.0f / std::sqrt(x); }
 // sincosf is provided by glibc
+static inline void sincospif(float x, float* s, float* c) { sincosf(3.14159265358979323846f * x, s, c); }
 using std::max;
 using std::min;
 
