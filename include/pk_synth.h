@@ -793,6 +793,51 @@ int pk_resample_tile_samples(pk_resample* h, int32_t* tile);
 int pk_resample_run(pk_resample* h, const float* wav, const int32_t* lens, int32_t B, float* out, int32_t flags);
 void pk_resample_destroy(pk_resample* h);
 
+/* ------------------------------------------------------------------ pitch */
+/* Frame-level f0 of ragged batches (csrc/pitch.hip) behind the reference's Pitch (parakeet/data/get_feats.py:91-164), which
+ * calls pyworld's DIO + StoneMask.  This is NOT that estimator: it is the project's own, defined in DESIGN 4.5e (the
+ * difference function, cumulative-mean normalisation, absolute threshold and parabolic refinement of YIN):
+ *   frames = n / hop + 1;  frame i reads L = win + tau_max samples from s = i * hop - L / 2, zeros outside the utterance
+ *   d(tau)  = sum_{j < win} (x[s + j] - x[s + j + tau])^2,  tau = 1 ... tau_max   (fp32, j ascending, one chain per lag)
+ *   d'(tau) = d(tau) * tau / c(tau) with c(tau) = d(1) + ... + d(tau), 1 where c(tau) is not > 0;  d'(0) = 1
+ *   tau0 = the smallest tau in [tau_min, tau_max - 1] with d'(tau) < threshold; none: lag 0, f0 0 (unvoiced)
+ *   tau* = tau0, then + 1 while tau* + 1 <= tau_max - 1 and d'(tau* + 1) < d'(tau*)
+ *   a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1);  delta = (a - c) / (2 (a - 2 b + c)) if a >= b, c >= b and
+ *   a - 2 b + c > 0, else 0;  f0 = sr / (tau* + delta)  (the refinement in float64 on the fp32 d', rounded once)
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): 2 <= tau_min <= tau_max - 2, tau_max <= 960,
+ * 1 <= win <= 2 * tau_max, 1 <= hop <= 16384.  PK_EINVAL: sr < 1, a threshold that is not a number. */
+typedef struct pk_pitch pk_pitch;
+typedef struct {
+    int32_t sr;
+    int32_t hop;
+    int32_t tau_min;
+    int32_t tau_max;
+    int32_t win;
+    float threshold;
+} pk_pitch_cfg;
+int pk_pitch_create(pk_ctx* ctx, const pk_pitch_cfg* cfg, pk_pitch** out);
+/* frames = n_samples / hop + 1, 0 <= n_samples < 2^31 (else PK_EINVAL). */
+int pk_pitch_frames(pk_pitch* h, int64_t n_samples, int32_t* frames);
+/* Frames per workgroup.  Tiles start at utterance-relative multiples of it. */
+int pk_pitch_tile_frames(pk_pitch* h, int32_t* tile);
+/* wav: packed samples of B utterances, lens (B, host) >= 1 each.  Packed by utterance: f0_out one float per frame (0 for an
+ * unvoiced frame), lag_out (NULL: not wanted) one int32 tau* per frame (0 for unvoiced), cmnd_out (NULL: not wanted)
+ * tau_max + 1 floats d'(0 ... tau_max) per frame.  A frame depends on its own samples only: an utterance's result is
+ * bit-identical alone, in any batch and at any position in it; its neighbours in the packed buffer are never read.
+ * PK_EINVAL: NULL h / wav / lens / f0_out, B <= 0, an empty utterance.
+ * flags: PK_HOST_IO if wav and the outputs are host pointers (then synchronous). */
+int pk_pitch_run(pk_pitch* h, const float* wav, const int32_t* lens, int32_t B, float* f0_out, int32_t* lag_out,
+                 float* cmnd_out, int32_t flags);
+void pk_pitch_destroy(pk_pitch* h);
+/* Pitch._convert_to_continuous_f0 (get_feats.py:99-119) and the log step of _calculate_f0 (:136-138) for B packed f0
+ * tracks, from any estimator: frames before the first / after the last non-zero value take that value, a zero frame i
+ * between non-zero neighbours a < i < b takes f(a) + (f(b) - f(a)) (i - a) / (b - a) (float64, rounded once), a track
+ * without a non-zero value is returned as it is; with bit 0 of log_flag every non-zero result v becomes log(v) (float64,
+ * rounded once); bit 1 leaves the filling out (the reference's use_continuous_f0 = False: the log step alone).
+ * f0, out: DEVICE, packed, out must not overlap f0; frames (B, host) >= 1 each, of any length.  Synchronises.
+ * PK_EINVAL: NULL pointer, B <= 0, an empty track, a log_flag outside 0 ... 3. */
+int pk_op_continuous_f0(pk_ctx* ctx, const float* f0, const int32_t* frames, int32_t B, int32_t log_flag, float* out);
+
 /* ------------------------------------------- multi-resolution STFT distance */
 /* parakeet/modules/stft_loss.py: what MultiResolutionSTFTLoss (:163-219) needs of two signals, reduced on the device.
  * A handle holds R resolutions.  n_fft must be a multiple of 16 (else PK_EUNSUPPORTED); hop_length is ANY integer >= 1

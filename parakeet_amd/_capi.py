@@ -107,6 +107,11 @@ class ResampleCfg(C.Structure):
     _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("taps", C.c_int32)]
 
 
+class PitchCfg(C.Structure):
+    _fields_ = [("sr", C.c_int32), ("hop", C.c_int32), ("tau_min", C.c_int32), ("tau_max", C.c_int32), ("win", C.c_int32),
+                ("threshold", C.c_float)]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -267,6 +272,12 @@ def _declare(lib):
         "pk_resample_tile_samples": (C.c_int, [vp, i32p]),
         "pk_resample_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
         "pk_resample_destroy": (None, [vp]),
+        "pk_pitch_create": (C.c_int, [vp, C.POINTER(PitchCfg), C.POINTER(vp)]),
+        "pk_pitch_frames": (C.c_int, [vp, i64, i32p]),
+        "pk_pitch_tile_frames": (C.c_int, [vp, i32p]),
+        "pk_pitch_run": (C.c_int, [vp, f32p, i32p, i32, f32p, C.c_void_p, f32p, i32]),
+        "pk_pitch_destroy": (None, [vp]),
+        "pk_op_continuous_f0": (C.c_int, [vp, f32p, i32p, i32, i32, f32p]),
         "pk_stftd_create": (C.c_int, [vp, C.POINTER(StftdCfg), C.POINTER(StftdRes), f32p, C.POINTER(vp)]),
         "pk_stftd_num_frames": (C.c_int, [vp, i32, i32, i32p]),
         "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),

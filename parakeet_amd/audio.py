@@ -14,6 +14,10 @@ csrc/istft.hip.
 ``resample_filter`` / ``Resample`` / ``resample`` / ``load_wav`` put audio of any rate on the model's rate: a polyphase
 Kaiser-windowed sinc defined in DESIGN.md 4.5d (this project's own filter; the reference calls ``librosa.load(path, sr=fs)``,
 whose resampler is not available here and is not reproduced), run by csrc/resample.hip.
+
+``Pitch`` / ``pitch_lags`` / ``continuous_f0_batch``: the reference's ``Pitch`` interface (get_feats.py:91-164) over this
+project's own f0 estimator (csrc/pitch.hip; NOT pyworld's DIO + StoneMask) and the reference's continuous-f0,
+log and token-average steps.
 """
 import ctypes as C
 import math
@@ -347,6 +351,157 @@ class Energy:
         if use_token_averaged_energy and duration is not None:
             energy = wrap(average_by_duration(energy, duration).reshape(-1, 1))
         return energy
+
+# ---- pitch -----------------------------------------------------------------------------------------------------------
+# the engine's envelope (csrc/pk_pitch.h)
+PITCH_MAX_TAU, PITCH_MAX_HOP = 960, 16384
+
+
+def pitch_lags(sr, f0min, f0max):
+    """(tau_min, tau_max) of DESIGN.md 4.5e: tau_max = ceil(sr / f0min), tau_min = max(2, floor(sr / f0max)); ``ValueError``
+    unless 0 < f0min < f0max, sr > 0 and tau_min <= tau_max - 2."""
+    if not sr > 0 or not f0min > 0 or not f0max > 0:
+        raise ValueError(f"pitch: sr = {sr}, f0min = {f0min}, f0max = {f0max} must be positive")
+    if not f0max > f0min:
+        raise ValueError(f"pitch: f0max = {f0max} must be above f0min = {f0min}")
+    tau_max = int(math.ceil(Fraction(sr) / Fraction(f0min)))
+    tau_min = max(2, int(math.floor(Fraction(sr) / Fraction(f0max))))
+    if tau_min > tau_max - 2:
+        raise ValueError(f"pitch: lags {tau_min} ... {tau_max} (sr = {sr}, f0min = {f0min}, f0max = {f0max}) leave no lag "
+                         "with a neighbour on either side: tau_min <= tau_max - 2 is needed")
+    return tau_min, tau_max
+
+
+def _check_pitch_envelope(hop_length, tau_max, win_length):
+    if tau_max > PITCH_MAX_TAU:
+        raise NotImplementedError(f"pitch: tau_max = ceil(sr / f0min) = {tau_max} lags; the engine's limit is {PITCH_MAX_TAU} "
+                                  "(48 kHz at f0min = 50 Hz)")
+    if not 1 <= win_length <= 2 * tau_max:
+        raise NotImplementedError(f"pitch: win_length = {win_length}; the engine's limit is 1 ... 2 * tau_max = {2 * tau_max}")
+    if not 1 <= hop_length <= PITCH_MAX_HOP:
+        raise NotImplementedError(f"pitch: hop_length = {hop_length}; the engine's limit is 1 ... {PITCH_MAX_HOP}")
+
+
+def continuous_f0_batch(f0s, use_log_f0=False, device=None, fill=True):
+    """``Pitch._convert_to_continuous_f0`` (get_feats.py:99-119) for a ragged list of f0 tracks from ANY estimator, then the
+    natural log of the non-zero values if asked (:136-138): one engine call (``pk_op_continuous_f0``) -> list of (frames,)
+    device tensors.  ``fill=False`` leaves the unvoiced frames at zero (the reference's ``use_continuous_f0=False``)."""
+    ctx = Context.get(device)
+    xs = [ctx.to_device(f).reshape(-1) for f in f0s]
+    if not xs:
+        return []
+    frames = np.array([x.numel() for x in xs], dtype=np.int32)
+    if frames.min() < 1:
+        raise ValueError("continuous f0: an empty track")
+    x = xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+    out = ctx.empty((int(frames.sum()),))
+    _capi.check(ctx.lib.pk_op_continuous_f0(ctx.handle, dptr(x), frames.ctypes.data_as(C.POINTER(C.c_int32)), len(xs),
+                                            (1 if use_log_f0 else 0) | (0 if fill else 2), dptr(out)))
+    res, o = [], 0
+    for n in frames:
+        res.append(wrap(out[o:o + n]))
+        o += n
+    return res
+
+
+class Pitch:
+    """get_feats.py:91-164 on the device, with this project's estimator in place of pyworld's.
+
+    The reference's ``_calculate_f0`` calls DIO + StoneMask (third-party C++); what runs here is NOT that: it is the estimator
+    defined in DESIGN.md 4.5e (YIN's difference function, cumulative-mean normalisation, absolute ``threshold`` and
+    parabolic refinement; csrc/pitch.hip), which returns f0 in Hz on the same frame grid (``len(wav) // hop_length + 1``
+    frames) with its own voicing decisions.  Everything after the estimator is the reference's: continuous f0, the log of the
+    non-zero values, token averages.  Results are device tensors, as ``Energy`` returns them."""
+
+    def __init__(self, sr=24000, hop_length=300, f0min=80, f0max=7600, *, threshold=0.1, win_length=None, device=None):
+        self.sr, self.hop_length, self.f0min, self.f0max = sr, hop_length, f0min, f0max
+        self.tau_min, self.tau_max = pitch_lags(sr, f0min, f0max)
+        if int(sr) != sr or int(hop_length) != hop_length or hop_length < 1:
+            raise ValueError(f"pitch: sr = {sr} and hop_length = {hop_length} must be positive integers")
+        if not 0 < threshold:
+            raise ValueError(f"pitch: threshold = {threshold} must be positive")
+        self.threshold = float(threshold)
+        self.win_length = 2 * self.tau_max if win_length is None else int(win_length)
+        _check_pitch_envelope(int(hop_length), self.tau_max, self.win_length)
+        self._device = device
+        self.ctx = Context.get(device)
+        cfg = _capi.PitchCfg(int(sr), int(hop_length), self.tau_min, self.tau_max, self.win_length, self.threshold)
+        h = C.c_void_p()
+        _capi.check(self.ctx.lib.pk_pitch_create(self.ctx.handle, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.ctx.lib.pk_pitch_destroy(h)
+            except Exception:
+                pass
+
+    def frames(self, n):
+        return int(n) // int(self.hop_length) + 1
+
+    @property
+    def tile_frames(self):
+        """Frames per workgroup of the engine's kernel."""
+        t = C.c_int32()
+        _capi.check(self.ctx.lib.pk_pitch_tile_frames(self.h, C.byref(t)))
+        return t.value
+
+    def _run(self, wavs, want_lag=False, want_cmnd=False):
+        ctx = Context.get(self._device)
+        xs = [ctx.to_device(w).reshape(-1) for w in wavs]
+        lens = np.array([x.numel() for x in xs], dtype=np.int32)
+        if lens.size == 0 or lens.min() < 1:
+            raise ValueError("Pitch: an empty signal")
+        x = xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+        nf = [self.frames(n) for n in lens]
+        total = sum(nf)
+        f0 = ctx.empty((total,))
+        lag = torch.empty((total,), dtype=torch.int32, device=f0.device) if want_lag else None
+        cm = ctx.empty((total, self.tau_max + 1)) if want_cmnd else None
+        _capi.check(ctx.lib.pk_pitch_run(self.h, dptr(x), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(xs), dptr(f0),
+                                         None if lag is None else C.c_void_p(lag.data_ptr()),
+                                         None if cm is None else dptr(cm), 0))
+        split = lambda t: None if t is None else list(torch.split(t, nf))   # noqa: E731
+        return split(f0), split(lag), split(cm)
+
+    def track(self, wavs):
+        """Ragged list -> per utterance ``(f0_raw, lag)``: (frames,) float32 Hz (0 for unvoiced) and int32 lags (0)."""
+        f0, lag, _ = self._run(list(wavs), want_lag=True)
+        return [(wrap(a), b) for a, b in zip(f0, lag)]
+
+    def cmnd(self, wav):
+        """(frames, tau_max + 1): the cumulative-mean-normalised difference d'(0 ... tau_max) of every frame."""
+        return wrap(self._run([wav], want_cmnd=True)[2][0])
+
+    def _convert_to_continuous_f0(self, f0):
+        return continuous_f0_batch([f0], False, self._device)[0]
+
+    def _calculate_f0(self, input, use_continuous_f0=True, use_log_f0=True):   # noqa: A002  (the reference's argument name)
+        return self.get_pitch_batch([input], None, use_continuous_f0, use_log_f0)[0]
+
+    def _average_by_duration(self, input, d):   # noqa: A002
+        return wrap(average_by_duration(Context.get(self._device).to_device(input).reshape(-1), d).reshape(-1, 1))
+
+    def get_pitch(self, wav, use_continuous_f0=True, use_log_f0=True, use_token_averaged_f0=True, duration=None):
+        """(frames,) f0, or with ``duration`` its token averages (T, 1) like the reference's."""
+        f0 = self._calculate_f0(wav, use_continuous_f0, use_log_f0)
+        if use_token_averaged_f0 and duration is not None:
+            f0 = self._average_by_duration(f0, duration)
+        return f0
+
+    def get_pitch_batch(self, wavs, durations=None, use_continuous_f0=True, use_log_f0=True, use_token_averaged_f0=True):
+        """``get_pitch`` for a ragged list: one engine call for the estimator and one for the continuous / log step."""
+        wavs = list(wavs)
+        f0 = self._run(wavs)[0]
+        if use_continuous_f0 or use_log_f0:
+            f0 = continuous_f0_batch(f0, use_log_f0, self._device, fill=use_continuous_f0)
+        f0 = [wrap(f) for f in f0]
+        if use_token_averaged_f0 and durations is not None:
+            f0 = [self._average_by_duration(f, d) for f, d in zip(f0, durations)]
+        return f0
+
 
 # ---- resampling ------------------------------------------------------------------------------------------------------
 # name -> (zeros, rolloff, beta): the number of zero crossings kept on each side (at the lower of the two rates), the cutoff as
