@@ -7,7 +7,8 @@
 //
 // Per layer:
 //   XG = X . W_ih^T + (b_ih + b_hh) for every (partial, step) row: ONE launch of the dense GEMM (pk_fft_run_dense; layer 0
-//   reads the mel frames zero-padded to a multiple of 32 channels, so that the split-fp16 GEMM takes any n_mels).
+//   reads the mel frames zero-padded to a multiple of 32 channels, so that the split-fp16 GEMM takes any n_mels; above
+//   SPK_GEMM_MAX_IN channels k_spk_proj_wide sums layer 0 in fp64 instead).
 //   k_spk_lstm_rec: one workgroup owns a tile of SPK_M = 32 partials and walks all T steps; no communication between
 //   workgroups.  Per step the tile's 32 x 4H gate block h(t-1) . W_hh^T runs on the matrix cores, W_hh^T streamed from L2
 //   in the MFMA operand layout packed at finalize.  Wave w owns the 32-unit blocks ub = w, w + 8, ...: it accumulates the
@@ -42,6 +43,8 @@ typedef pk_fft_dense Dense;
 constexpr int SPK_M = 32;          // partials per workgroup (one MFMA row block)
 constexpr int SPK_WAVES = 8;
 constexpr int SPK_MAX_H = 512;
+constexpr int SPK_GEMM_MAX_IN = 512;   // layer 0 above this many mel channels: k_spk_proj_wide instead of the tile GEMM
+constexpr int SPK_WIDE_ROWS = 8;
 
 struct RecArgs {
     const float* xg;      // [P * T][4H]: x W_ih^T + b_ih + b_hh, row p * T + t
@@ -113,18 +116,14 @@ __global__ __launch_bounds__(SPK_WAVES * 64) void k_spk_lstm_rec(RecArgs a) {
         for (int s = 0; s < UBW; ++s) {
             const int ub = wave + s * SPK_WAVES;
             if (ub >= nub) break;   // wave-uniform
-            // the accumulators start as this step's input projections, brought to the scale of the products (a power of
-            // two: exact); the loads are independent of h and overlap the matrix loop
+            // the accumulators start at zero and this step's input projection is added once, behind the matrix loop.  (Seeded
+            // with xg, each of the H / 2 (F32) or 3 H / 16 (F16X3) accumulation steps rounded at the magnitude of xg + partial sum
+            // instead of the partial sum's: 2.5 x the error at H = 512, tests/test_spk_lstm_gpu.py.)
             f32x16 acc[4];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mfma_row(r, hi);
-                const long p = p0 + row;
-                const float* xr = a.xg + (p * T + t) * G + ub * 32 + j;
-                const float up = SPLIT ? pow2f((t == 0 ? rexp[row] : PK_UNIT_EXP) + a.kw) : 1.f;
+            for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q][r] = p < P ? xr[q * H] * up : 0.f;
-            }
+                for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
             if constexpr (SPLIT) {
                 const int KC = H / 16;
                 const f16x8* wb = reinterpret_cast<const f16x8*>(a.w) + (long)ub * KC * 8 * 64 + lane;
@@ -163,11 +162,21 @@ __global__ __launch_bounds__(SPK_WAVES * 64) void k_spk_lstm_rec(RecArgs a) {
             // the cell, in registers
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float sc = SPLIT ? pow2f(-((t == 0 ? rexp[mfma_row(r, hi)] : PK_UNIT_EXP) + a.kw)) : 1.f;
-                const float gi = sigmoidf_(acc[0][r] * sc);
-                const float gf = sigmoidf_(acc[1][r] * sc);
-                const float gg = tanhf(acc[2][r] * sc);
-                const float go = sigmoidf_(acc[3][r] * sc);
+                const int row = mfma_row(r, hi);
+                // rows behind P read the last partial's xg: unconditional loads that the compiler may issue together (behind a
+                // guard each waited for its own latency); what those rows compute is never stored and feeds no other row.
+                // (32-bit offsets: pk_spk_embed admits at most 2^30 elements of xg; they halve the address registers)
+                const long p = p0 + row < P ? p0 + row : P - 1;
+                const float* xr = a.xg + (unsigned)((p * T + t) * G + ub * 32 + j);
+                // the products come back from their scale by a power of two (exact)
+                const float sc = SPLIT ? pow2f(-((t == 0 ? rexp[row] : PK_UNIT_EXP) + a.kw)) : 1.f;
+                float g4[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) g4[q] = acc[q][r] * sc + xr[q * H];
+                const float gi = sigmoidf_(g4[0]);
+                const float gf = sigmoidf_(g4[1]);
+                const float gg = tanhf(g4[2]);
+                const float go = sigmoidf_(g4[3]);
                 const float c = gf * cst[s][r] + gi * gg;
                 cst[s][r] = c;
                 hnew[s][r] = go * tanhf(c);
@@ -271,6 +280,32 @@ __global__ __launch_bounds__(256) void k_spk_pad_in(const float* __restrict__ in
     }
 }
 
+// Layer 0 for n_mels > SPK_GEMM_MAX_IN: xg = in . W_ih^T + b with fp64 accumulators.  The tile GEMM sums K products in one fp32
+// accumulator, k ascending; a power mel spreads over decades, the partial sums of thousands of terms reach 50 - 100 and every
+// step rounds at that magnitude (n_mels 4096: 2.6 - 3.1 x the bar of tests/test_spk_lstm_gpu.py, reproduced by an fp32
+// restatement summed one k at a time).  One thread per gate column and SPK_WIDE_ROWS rows; kn is W_ih^T [n_mels][G].
+__global__ __launch_bounds__(256) void k_spk_proj_wide(const float* __restrict__ in, long rows, int C, const float* __restrict__ kn,
+                                                       const float* __restrict__ bias, int G, float* __restrict__ xg) {
+    const int g = blockIdx.y * 256 + threadIdx.x;
+    const long r0 = (long)blockIdx.x * SPK_WIDE_ROWS;
+    if (g >= G) return;
+    double acc[SPK_WIDE_ROWS];
+    const float* src[SPK_WIDE_ROWS];
+#pragma unroll
+    for (int i = 0; i < SPK_WIDE_ROWS; ++i) {
+        acc[i] = 0.0;
+        src[i] = in + (r0 + i < rows ? r0 + i : rows - 1) * C;   // rows behind the end repeat the last one and are not stored
+    }
+    for (int k = 0; k < C; ++k) {
+        const double w = kn[(long)k * G + g];
+#pragma unroll
+        for (int i = 0; i < SPK_WIDE_ROWS; ++i) acc[i] = fma((double)src[i][k], w, acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < SPK_WIDE_ROWS; ++i)
+        if (r0 + i < rows) xg[(r0 + i) * G + g] = (float)(acc[i] + (double)bias[g]);
+}
+
 uint16_t f32_to_f16_bits(float v) {
     const _Float16 h = (_Float16)v;
     uint16_t b;
@@ -293,6 +328,7 @@ struct pk_spk : pk_fft_core {
     std::vector<size_t> whh32, whh16;   // per layer: packed W_hh^T (F32 floats / F16X3 halves)
     std::vector<int> kw;                // per layer: exponent of the split weights
     size_t lin_w = 0, lin_b = 0;
+    size_t wide_kn = 0, wide_b = 0;     // n_mels > SPK_GEMM_MAX_IN: W_ih^T [n_mels][4H] and b_ih + b_hh of layer 0, fp32
     pk_dbuf d_x, d_xg, d_hseq, d_hlast, d_cu;
     pk_dbuf d_ge2e;                     // pk_spk_ge2e: row terms, speaker sums, transposed centroids
     std::vector<int32_t> cu_h;          // host copy of the last call's utterance bounds (source of its async copy)
@@ -382,7 +418,12 @@ extern "C" int pk_spk_finalize(pk_spk* h) {
             for (int k = 0; k < in; ++k) kn[(size_t)k * G + g] = (*wih)[(size_t)g * in + k];
             bias[g] = (*bih)[g] + (*bhh)[g];
         }
-        PK_TRY(pk_fft_add_dense_kn(ar, kn, &bias, cin, 1, G, h->xin[l]));
+        if (l == 0 && c.n_mels > SPK_GEMM_MAX_IN) {
+            h->wide_kn = ar.put(kn);
+            h->wide_b = ar.put(bias);
+        } else {
+            PK_TRY(pk_fft_add_dense_kn(ar, kn, &bias, cin, 1, G, h->xin[l]));
+        }
         // W_hh^T in the operand layouts of k_spk_lstm_rec: lane (j, hi) of the wave owning unit block ub, gate q
         const std::vector<float>& W = *whh;   // [4H][H]
         const int nub = H / 32;
@@ -462,11 +503,12 @@ extern "C" int pk_spk_embed(pk_spk* h, const float* partials, int32_t P, int32_t
         PK_HIP(hipEventRecord(h->cu_ev, ctx->stream));
         dcu = h->d_cu.as<int>();
     }
-    PK_TRY(pk_fft_act_reserve(h->d_x, (int)rows, h->cin0));
+    const bool wide = c.n_mels > SPK_GEMM_MAX_IN;   // layer 0 reads the partials themselves (k_spk_proj_wide)
+    if (!wide) PK_TRY(pk_fft_act_reserve(h->d_x, (int)rows, h->cin0));
     PK_TRY(pk_fft_act_reserve(h->d_xg, (int)rows, G));
     if (L > 1) PK_TRY(pk_fft_act_reserve(h->d_hseq, (int)rows, H));
     PK_TRY(h->d_hlast.reserve((size_t)P * H * sizeof(float)));
-    float* x = pk_fft_act_ptr(h->d_x, h->cin0);
+    float* x = wide ? nullptr : pk_fft_act_ptr(h->d_x, h->cin0);
     float* xg = pk_fft_act_ptr(h->d_xg, G);
     float* hseq = L > 1 ? pk_fft_act_ptr(h->d_hseq, H) : nullptr;
     // the GEMM tiles read rows up to the next multiple of 128 beyond P * T: only that tail is cleared (the rows below are
@@ -476,17 +518,22 @@ extern "C" int pk_spk_embed(pk_spk* h, const float* partials, int32_t P, int32_t
         if (off < buf.cap) PK_HIP(hipMemsetAsync((char*)buf.p + off, 0, buf.cap - off, ctx->stream));
         return PK_OK;
     };
-    PK_TRY(clear_tail(h->d_x, x, h->cin0));
+    if (!wide) PK_TRY(clear_tail(h->d_x, x, h->cin0));
     if (L > 1) PK_TRY(clear_tail(h->d_hseq, hseq, H));
-    {
+    if (!wide) {
         const long n = rows * h->cin0;
         const int grid = (int)std::min<long>((n + 255) / 256, 16384);
         PK_LAUNCH(ctx, "spk_pad_in", k_spk_pad_in, dim3(grid), dim3(256), 0, partials, rows, c.n_mels, h->cin0, x);
     }
     for (int l = 0; l < L; ++l) {
         const float* A = l == 0 ? x : hseq;
-        PK_TRY(pk_fft_run_dense(h, "spk_gemm_xg", h->xin[l], A, l == 0 ? h->cin0 : H, xg, G, (int)rows, PK_ACT_NONE, nullptr, 0,
-                                nullptr));
+        if (l == 0 && wide) {
+            PK_LAUNCH(ctx, "spk_proj_wide", k_spk_proj_wide, dim3((unsigned)pk_div_up(rows, (long)SPK_WIDE_ROWS), pk_div_up(G, 256)),
+                      dim3(256), 0, partials, rows, c.n_mels, h->W(h->wide_kn), h->W(h->wide_b), G, xg);
+        } else {
+            PK_TRY(pk_fft_run_dense(h, "spk_gemm_xg", h->xin[l], A, l == 0 ? h->cin0 : H, xg, G, (int)rows, PK_ACT_NONE, nullptr, 0,
+                                    nullptr));
+        }
         RecArgs ra;
         ra.xg = xg;
         ra.kw = h->kw[l];

@@ -12,45 +12,50 @@ import torch
 from oracle import audio_ref
 
 
-def _t(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.float64)
+def _t(a, dtype=torch.float64):
+    return torch.as_tensor(np.asarray(a), dtype=dtype)
 
 
-def lstm_last_hidden(state, x, num_layers, initial_states=None):
-    """x (B, T, C) -> h(T) of the last layer (B, H), fp64."""
-    h_in = _t(x)
+def lstm_last_hidden(state, x, num_layers, initial_states=None, dtype=torch.float64, return_layers=False, rec_matmul=None):
+    """x (B, T, C) -> h(T) of the last layer (B, H), evaluated in ``dtype`` (float64: the oracle; float32: its own
+    rounding, for error bars).  return_layers: also the list of every layer's h sequence (B, T, H).  rec_matmul(h, whh):
+    another evaluation of the recurrent product h @ whh.T (another summation order, for the same purpose)."""
+    h_in = _t(x, dtype)
     B, T, _ = h_in.shape
+    layers = []
     for layer in range(num_layers):
-        wih, whh = _t(state[f"lstm.weight_ih_l{layer}"]), _t(state[f"lstm.weight_hh_l{layer}"])
-        b = _t(state[f"lstm.bias_ih_l{layer}"]) + _t(state[f"lstm.bias_hh_l{layer}"])
+        wih, whh = _t(state[f"lstm.weight_ih_l{layer}"], dtype), _t(state[f"lstm.weight_hh_l{layer}"], dtype)
+        b = _t(state[f"lstm.bias_ih_l{layer}"], dtype) + _t(state[f"lstm.bias_hh_l{layer}"], dtype)
         H = whh.shape[1]
         if initial_states is None:
-            h = torch.zeros(B, H, dtype=torch.float64)
-            c = torch.zeros(B, H, dtype=torch.float64)
+            h = torch.zeros(B, H, dtype=dtype)
+            c = torch.zeros(B, H, dtype=dtype)
         else:
-            h, c = _t(initial_states[0][layer]), _t(initial_states[1][layer])
+            h, c = _t(initial_states[0][layer], dtype), _t(initial_states[1][layer], dtype)
         xg = h_in @ wih.T + b
         outs = []
         for t in range(T):
-            g = xg[:, t] + h @ whh.T
+            g = xg[:, t] + (h @ whh.T if rec_matmul is None else rec_matmul(h, whh))
             i, f, gg, o = g.split(H, dim=1)
             c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
             h = torch.sigmoid(o) * torch.tanh(c)
             outs.append(h)
         h_in = torch.stack(outs, 1)
-    return h
+        layers.append(h_in)
+    return (h, layers) if return_layers else h
 
 
 def normalize(x, axis):
     return x / torch.clamp(torch.linalg.norm(x, dim=axis, keepdim=True), min=1e-12)
 
 
-def embed_sequences(state, x, num_layers, initial_states=None, reduce=False):
-    h = lstm_last_hidden(state, x, num_layers, initial_states)
-    e = normalize(torch.relu(h @ _t(state["linear.weight"]) + _t(state["linear.bias"])), 1)
+def embed_sequences(state, x, num_layers, initial_states=None, reduce=False, dtype=torch.float64, return_layers=False,
+                    rec_matmul=None):
+    h, layers = lstm_last_hidden(state, x, num_layers, initial_states, dtype, True, rec_matmul)
+    e = normalize(torch.relu(h @ _t(state["linear.weight"], dtype) + _t(state["linear.bias"], dtype)), 1)
     if reduce:
-        return normalize(e.mean(0), 0)
-    return e
+        e = normalize(e.mean(0), 0)
+    return (e, layers) if return_layers else e
 
 
 def power_mel(wav, sr=16000, n_fft=400, hop=160, n_mels=40):
