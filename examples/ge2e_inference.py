@@ -10,8 +10,9 @@ engine in batches of ``--batch`` utterances, each ONE ``embed_utterances`` call 
 ``--config`` is a YAML file with ``data`` / ``model`` sections overriding examples/ge2e/config.py's defaults; ``--opts``
 takes ``KEY VALUE`` pairs such as ``data.n_mels 40``.  Files: PCM or float WAV; other rates are resampled with
 scipy.signal.resample_poly on the host (``--resampler scipy``, the default) or by the engine's polyphase kernel
-(``--resampler engine``); neither is librosa's resampler.  Silence trimming is skipped (no webrtcvad), as the reference
-does without that package.
+(``--resampler engine``); neither is librosa's resampler.  Silence trimming is skipped by default (no webrtcvad), as the reference
+does without that package; ``--vad energy`` runs the reference's ``trim_long_silences`` on the engine behind this project's
+energy detector (NOT webrtcvad: ``parakeet_amd.audio.trim_long_silences``).
 """
 import argparse
 import ast
@@ -64,6 +65,8 @@ def main():
     ap.add_argument("--device", type=str, choices=["cpu", "gpu"], default="gpu", help="ignored: the engine is the GPU")
     ap.add_argument("--batch", type=int, default=1024, help="utterances per engine call")
     ap.add_argument("--resampler", choices=["scipy", "engine"], default="scipy", help="what resamples files at other rates")
+    ap.add_argument("--vad", choices=["none", "energy"], default="none",
+                    help="trim long silences before the partials are cut: 'energy' is the engine's energy detector, not webrtcvad")
     ap.add_argument("--opts", nargs=argparse.REMAINDER, help="KEY VALUE pairs overriding --config and the defaults")
     args = ap.parse_args()
     cfg = load_config(args.config, args.opts)
@@ -77,7 +80,7 @@ def main():
         vad_max_silence_length=c["vad_max_silence_length"], mel_window_length=c["mel_window_length"],
         mel_window_step=c["mel_window_step"], n_mels=c["n_mels"], partial_n_frames=c["partial_n_frames"],
         min_pad_coverage=c["min_pad_coverage"], partial_overlap_ratio=c["min_pad_coverage"],   # sic: inference.py:81
-        resampler=args.resampler)
+        resampler=args.resampler, vad=None if args.vad == "none" else args.vad)
     input_dir = Path(args.input).expanduser()
     output_dir = Path(args.output).expanduser()
     ifpaths = sorted(input_dir.rglob(args.pattern))

@@ -5,7 +5,8 @@ reference wav -> GE2E embedding (256) -> Tacotron2(d_global_condition=256, the n
 
 The notebook's text front end (chinese_g2p.convert_sentence: pypinyin / jieba) is not available, so ``--text`` holds
 one ``utt_id | PHONE_IDS | TONE_IDS`` line per sentence (space-separated ids of aishell3's voc_phones / voc_tones).
-The speaker embedding uses the notebook's preprocessor (partial overlap 0.5).  All sentences are decoded as one
+The speaker embedding uses the notebook's preprocessor (partial overlap 0.5); ``--vad energy`` trims the reference wav's long
+silences first (the engine's energy detector, NOT webrtcvad; off by default).  All sentences are decoded as one
 ragged batch conditioned on the same voice.
 """
 import argparse
@@ -52,9 +53,11 @@ def main():
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--max_decoder_steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0, help="decoder-prenet dropout stream")
+    ap.add_argument("--vad", choices=["none", "energy"], default="none",
+                    help="trim the reference wav's long silences: 'energy' is the engine's energy detector, not webrtcvad")
     args = ap.parse_args()
 
-    p = ge2e_preprocessor(overlap=0.5)
+    p = ge2e_preprocessor(overlap=0.5, vad=None if args.vad == "none" else args.vad)
     encoder = checkpoint.load_ge2e(args.ge2e_checkpoint)
     embed = encoder.embed_utterance(p.extract_mel_partials(p.preprocess_wav(args.ref_audio)))
 

@@ -838,6 +838,50 @@ void pk_pitch_destroy(pk_pitch* h);
  * PK_EINVAL: NULL pointer, B <= 0, an empty track, a log_flag outside 0 ... 3. */
 int pk_op_continuous_f0(pk_ctx* ctx, const float* f0, const int32_t* frames, int32_t B, int32_t log_flag, float* out);
 
+/* ------------------------------------------------------- silence trimming */
+/* Framed power, the frame test of librosa.effects.trim / split, the reference's trim_long_silences
+ * (examples/ge2e/audio_processor.py:53-107) after its voice detector, and peak normalisation, for ragged batches
+ * (csrc/trim.hip).  Every pointer below is a DEVICE pointer unless it says host; packed means utterance after
+ * utterance.  An utterance's results are bit-identical alone, in any batch and at any position in it; its neighbours in the
+ * packed buffer are never read.
+ *   frames(N) = 1 + (N + 2 pad - Lf) / hop, pad = Lf / 2 (pad_mode 1, 2) or 0 (pad_mode 0; no frame when N < Lf);
+ *   P[i] = (1 / Lf) sum_{j < Lf} x~[i hop - pad + j]^2, x~ continued by reflection without repeating the edge (pad_mode 1,
+ *   needs N > Lf / 2) or by zeros (pad_mode 2); summed in fp32 in the order csrc/pk_trim.h states;
+ *   frame i is non-silent iff max(1e-10, P[i]) > max(1e-10, max_i P) * factor (in float64; factor = 10^(-top_db / 10));
+ *   start = first non-silent frame * hop, end = min(N, (last non-silent frame + 1) * hop); none: (0, 0).
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): 1 <= hop <= Lf <= 16384; window <= 16384;
+ * 1 <= avg_width <= 64; 0 <= max_silence <= 64.
+ * PK_EINVAL: NULL pointer, B <= 0, an empty utterance, an unknown pad_mode, reflect padding of N <= Lf / 2 samples. */
+typedef struct pk_trim pk_trim;
+int pk_trim_create(pk_ctx* ctx, pk_trim** out);       /* workspaces only: one handle serves every parameter set */
+void pk_trim_destroy(pk_trim* h);
+int pk_trim_num_frames(int64_t n_samples, int32_t frame_length, int32_t hop, int32_t pad_mode, int64_t* frames);
+/* Frames per workgroup of the power kernel.  Tiles start at utterance-relative multiples of it. */
+int pk_trim_tile_frames(int32_t frame_length, int32_t hop, int32_t* tile);
+/* lens (B, host).  power_out (NULL: a workspace): packed P, one float per frame; with rms != 0 its square root (then no
+ * flags and no bounds).  flags_out (NULL: not wanted): packed, one byte per frame, 1 = non-silent.  bounds_out (NULL: not
+ * wanted): (B, 2) int32 (start, end).  Two launches, no read-back. */
+int pk_trim_run(pk_trim* h, const float* wav, const int32_t* lens, int32_t B, int32_t frame_length, int32_t hop,
+                int32_t pad_mode, double factor, int32_t rms, float* power_out, uint8_t* flags_out, int32_t* bounds_out);
+/* trim_long_silences up to the gather.  n_w = N / window windows per utterance (the tail is dropped; n_w = 0 is allowed).
+ * Voice flags: voice_flags (packed, one byte per window) if not NULL -- from any detector --, else this project's energy
+ * detector, NOT webrtcvad: Q[k] = the window's power (frames with Lf = hop = window, no padding) and
+ * flag[k] iff Q[k] > max(max_k Q * rel, floor_power) (float64).  Then, as the reference: c = the set flags in
+ * [k - (W - 1) / 2, k + W / 2] inside the utterance, mask[k] iff 2 c > W (its moving average rounded half to even);
+ * keep[k] = any mask[k - (L - 1 - L / 2) ... k + L / 2], L = max_silence + 1 (its binary_dilation with ones(L)).
+ * pos_out: packed int32 per window: the window's index among the kept ones of its utterance, -1 if dropped.  kept (B, HOST):
+ * kept windows per utterance; the call synchronises to deliver it.  power_out / flags_out (NULL: not wanted): Q and the
+ * voice flags, packed.  wav may be NULL when voice_flags is given. */
+int pk_vad_mask(pk_trim* h, const float* wav, const int32_t* lens, int32_t B, int32_t window, int32_t avg_width,
+                int32_t max_silence, const uint8_t* voice_flags, double rel, double floor_power, float* power_out,
+                uint8_t* flags_out, int32_t* pos_out, int32_t* kept);
+/* out: packed, kept[b] * window samples per utterance: its kept windows in order.  pos, kept: as pk_vad_mask left them. */
+int pk_vad_gather(pk_trim* h, const float* wav, const int32_t* lens, int32_t B, int32_t window, const int32_t* pos,
+                  const int32_t* kept, float* out);
+/* out = y / max|y| per utterance, one correctly rounded division per sample; an utterance whose max|y| is below the smallest
+ * normal float is copied as it is.  out is packed like wav and must not overlap it. */
+int pk_peak_normalize(pk_trim* h, const float* wav, const int32_t* lens, int32_t B, float* out);
+
 /* ------------------------------------------- multi-resolution STFT distance */
 /* parakeet/modules/stft_loss.py: what MultiResolutionSTFTLoss (:163-219) needs of two signals, reduced on the device.
  * A handle holds R resolutions.  n_fft must be a multiple of 16 (else PK_EUNSUPPORTED); hop_length is ANY integer >= 1

@@ -27,6 +27,9 @@ PK_MEL_LOSS_ROWS = 16      # csrc/pk_mel_loss.h: map rows per tile of pk_mel_los
 # csrc/pk_seq_loss.h: entries per tile of pk_pair_loss_run / pk_bce_logits_run, rows x columns of pk_guided_attn_run's tile,
 # the longest fp32 accumulation chain of the three (0: float64 throughout)
 PK_SEQ_LOSS_PAIR_TILE, PK_SEQ_LOSS_GUIDE_ROWS, PK_SEQ_LOSS_GUIDE_COLS, PK_SEQ_LOSS_F32_CHAIN = 4096, 16, 64, 0
+# csrc/pk_trim.h: windows per scan step of the VAD mask kernel; the pad modes of pk_trim_run
+PK_TRIM_SCAN_CHUNK = 256
+PK_TRIM_PAD = {None: 0, "reflect": 1, "constant": 2}
 _EXC = {
     -1: ValueError,
     -2: AssertionError,
@@ -278,6 +281,15 @@ def _declare(lib):
         "pk_pitch_run": (C.c_int, [vp, f32p, i32p, i32, f32p, C.c_void_p, f32p, i32]),
         "pk_pitch_destroy": (None, [vp]),
         "pk_op_continuous_f0": (C.c_int, [vp, f32p, i32p, i32, i32, f32p]),
+        "pk_trim_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "pk_trim_destroy": (None, [vp]),
+        "pk_trim_num_frames": (C.c_int, [i64, i32, i32, i32, i64p]),
+        "pk_trim_tile_frames": (C.c_int, [i32, i32, i32p]),
+        "pk_trim_run": (C.c_int, [vp, f32p, i32p, i32, i32, i32, i32, C.c_double, i32, f32p, C.c_void_p, C.c_void_p]),
+        "pk_vad_mask": (C.c_int, [vp, f32p, i32p, i32, i32, i32, i32, C.c_void_p, C.c_double, C.c_double, f32p, C.c_void_p,
+                                  C.c_void_p, i32p]),
+        "pk_vad_gather": (C.c_int, [vp, f32p, i32p, i32, i32, C.c_void_p, i32p, f32p]),
+        "pk_peak_normalize": (C.c_int, [vp, f32p, i32p, i32, f32p]),
         "pk_stftd_create": (C.c_int, [vp, C.POINTER(StftdCfg), C.POINTER(StftdRes), f32p, C.POINTER(vp)]),
         "pk_stftd_num_frames": (C.c_int, [vp, i32, i32, i32p]),
         "pk_stftd_run": (C.c_int, [vp, f32p, f32p, i32p, i32, C.c_void_p, i32]),

@@ -503,6 +503,266 @@ class Pitch:
         return f0
 
 
+# ---- silence trimming ------------------------------------------------------------------------------------------------
+# DESIGN.md 4.5f.  The frame test of trim / split is librosa 0.8's (librosa is not a dependency: the definition in DESIGN.md is
+# the contract); everything after the voice detector in trim_long_silences is the reference's; the energy detector in front of
+# it is this project's own, NOT webrtcvad.  The engine's envelope (csrc/pk_trim.h):
+TRIM_MAX_FRAME, TRIM_MAX_AVG, TRIM_MAX_SILENCE = 16384, 64, 64
+_TRIM_HANDLES = {}
+
+
+class _TrimEngine:
+    """One ``pk_trim`` handle (workspaces only) per device."""
+
+    def __init__(self, device=None):
+        self.ctx = Context.get(device)
+        h = C.c_void_p()
+        _capi.check(self.ctx.lib.pk_trim_create(self.ctx.handle, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.ctx.lib.pk_trim_destroy(h)
+            except Exception:
+                pass
+
+
+def _trim_engine(device=None):
+    ctx = Context.get(device)
+    key = str(ctx.device)
+    if key not in _TRIM_HANDLES:
+        _TRIM_HANDLES[key] = _TrimEngine(device)
+    return _TRIM_HANDLES[key]
+
+
+def _pack(ctx, wavs, what):
+    """A ragged list -> (device tensors, lens int32, the packed buffer)."""
+    xs = [ctx.to_device(w).reshape(-1) for w in wavs]
+    lens = np.array([x.numel() for x in xs], dtype=np.int32)
+    if lens.size == 0 or lens.min() < 1:
+        raise ValueError(f"{what}: an empty signal")
+    return xs, lens, xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _vptr(t):
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
+def _check_frame_envelope(frame_length, hop_length):
+    if int(frame_length) != frame_length or int(hop_length) != hop_length or frame_length < 1 or hop_length < 1:
+        raise ValueError(f"frame_length = {frame_length} and hop_length = {hop_length} must be positive integers")
+    if frame_length > TRIM_MAX_FRAME:
+        raise NotImplementedError(f"frame_length = {frame_length}; the engine's limit is {TRIM_MAX_FRAME}")
+    if hop_length > frame_length:
+        raise NotImplementedError(f"hop_length = {hop_length}; the engine's limit is 1 ... frame_length = {frame_length}")
+
+
+def _pad_mode(center, pad_mode):
+    if not center:
+        return 0
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    return _capi.PK_TRIM_PAD[pad_mode]
+
+
+def trim_num_frames(n, frame_length, hop_length, center=True):
+    """1 + (n + 2 (frame_length // 2) - frame_length) // hop_length when centred, 1 + (n - frame_length) // hop_length (0 for
+    n < frame_length) when not."""
+    padded = int(n) + (2 * (int(frame_length) // 2) if center else 0)
+    return 0 if padded < frame_length else 1 + (padded - int(frame_length)) // int(hop_length)
+
+
+def trim_tile_frames(frame_length=2048, hop_length=512):
+    """Frames per workgroup of the engine's power kernel."""
+    _check_frame_envelope(frame_length, hop_length)
+    t = C.c_int32()
+    _capi.check(_capi.lib().pk_trim_tile_frames(int(frame_length), int(hop_length), C.byref(t)))
+    return t.value
+
+
+def _trim_run(wavs, frame_length, hop_length, center, pad_mode, top_db=None, rms=False, device=None):
+    """One engine call -> per utterance P (or its root), and with ``top_db`` the flags (bool) and a (B, 2) int32 device tensor
+    of (start, end); None where not asked for."""
+    _check_frame_envelope(frame_length, hop_length)
+    mode = _pad_mode(center, pad_mode)
+    sizes = [int(np.prod(w.shape)) if hasattr(w, "shape") else len(w) for w in wavs]
+    if not sizes or min(sizes) < 1:
+        raise ValueError("trim: an empty signal")
+    if mode == 1 and min(sizes) <= frame_length // 2:
+        raise ValueError(f"reflect padding needs more than frame_length // 2 = {frame_length // 2} samples, got {min(sizes)}")
+    eng = _trim_engine(device)
+    ctx = eng.ctx
+    xs, lens, x = _pack(ctx, wavs, "trim")
+    nf = [trim_num_frames(n, frame_length, hop_length, bool(center)) for n in lens]
+    power = ctx.empty((sum(nf),))
+    if sum(nf) == 0:                                   # center=False and no signal as long as a frame
+        return ([wrap(ctx.empty((0,))) for _ in xs], [ctx.empty((0,), torch.bool) for _ in xs],
+                torch.zeros((len(xs), 2), dtype=torch.int32, device=power.device))
+    flags = bounds = None
+    factor = 1.0
+    if top_db is not None:
+        factor = 10.0 ** (-float(top_db) / 10.0)
+        flags = torch.empty((sum(nf),), dtype=torch.bool, device=power.device)    # (the kernel writes bytes 0 / 1)
+        bounds = torch.empty((len(xs), 2), dtype=torch.int32, device=power.device)
+    _capi.check(ctx.lib.pk_trim_run(eng.h, dptr(x), _i32p(lens), len(xs), int(frame_length), int(hop_length), mode, factor,
+                                    1 if rms else 0, _vptr(power), _vptr(flags), _vptr(bounds)))
+    P = [wrap(p) for p in torch.split(power, nf)]
+    F = None if flags is None else list(torch.split(flags, nf))
+    return P, F, bounds
+
+
+def frame_power(wavs, frame_length=2048, hop_length=512, center=True, pad_mode="reflect", device=None):
+    """A ragged list of signals -> a list of (frames,) device tensors: the mean of x^2 over every frame.
+    ``center=False``: no padding, frames at multiples of the hop.  One engine call."""
+    return _trim_run(list(wavs), frame_length, hop_length, center, pad_mode, device=device)[0]
+
+
+def rms(wavs, frame_length=2048, hop_length=512, center=True, pad_mode="reflect", device=None):
+    """The square root of ``frame_power`` (``librosa.feature.rms`` per utterance, without the leading axis)."""
+    return _trim_run(list(wavs), frame_length, hop_length, center, pad_mode, rms=True, device=device)[0]
+
+
+def nonsilent_frames_batch(wavs, top_db=60, frame_length=2048, hop_length=512, pad_mode="reflect", device=None):
+    """A list of (frames,) bool device tensors: frame i is non-silent iff 10 log10(max(1e-10, P[i])) - 10 log10(max(1e-10,
+    max P)) > -top_db (librosa 0.8's ``_signal_to_frame_nonsilent`` with ``ref=np.max``)."""
+    return _trim_run(list(wavs), frame_length, hop_length, True, pad_mode, top_db=top_db, device=device)[1]
+
+
+def trim_batch(wavs, top_db=60, frame_length=2048, hop_length=512, pad_mode="reflect", device=None):
+    """``trim`` for a ragged list in one engine call -> (list of slices ``y[start:end]``, (B, 2) int64 numpy array).  The
+    slices are views of what was passed in (numpy stays numpy, a tensor stays a tensor); the only read-back is the B pairs."""
+    wavs = list(wavs)
+    index = _trim_run(wavs, frame_length, hop_length, True, pad_mode, top_db=top_db, device=device)[2].cpu().numpy().astype(np.int64)
+    wavs = [w if isinstance(w, (np.ndarray, torch.Tensor)) else np.asarray(w) for w in wavs]
+    return [w.reshape(-1)[a:b] for w, (a, b) in zip(wavs, index)], index
+
+
+def trim(y, top_db=60, frame_length=2048, hop_length=512, pad_mode="reflect", device=None):
+    """``librosa.effects.trim`` for a 1-D signal: ``(y[start:end], np.array([start, end]))`` with start = the first non-silent
+    frame * hop, end = min(len(y), (the last one + 1) * hop), (0, 0) without one.  The slice is a view."""
+    out, index = trim_batch([y], top_db, frame_length, hop_length, pad_mode, device)
+    return out[0], index[0]
+
+
+def split(y, top_db=60, frame_length=2048, hop_length=512, pad_mode="reflect", device=None):
+    """``librosa.effects.split``: the runs of non-silent frames as an (n, 2) int64 array of sample intervals, the last end
+    clipped to len(y).  The flags come from the device, the runs are found on the host."""
+    flags = nonsilent_frames_batch([y], top_db, frame_length, hop_length, pad_mode, device)[0].cpu().numpy()
+    n = int(np.asarray(y.shape).prod()) if hasattr(y, "shape") else len(y)
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], flags.astype(np.int8), [0]])))
+    return np.minimum(edges.reshape(-1, 2).astype(np.int64) * int(hop_length), n)
+
+
+def peak_normalize_batch(wavs, device=None):
+    """y / max|y| per utterance (``librosa.util.normalize`` of a 1-D signal with its defaults), one rounding per sample; an
+    utterance whose max|y| is below float32's smallest normal number comes back unchanged.  A list of device tensors."""
+    eng = _trim_engine(device)
+    ctx = eng.ctx
+    xs, lens, x = _pack(ctx, list(wavs), "peak_normalize")
+    out = ctx.empty((int(lens.sum()),))
+    _capi.check(ctx.lib.pk_peak_normalize(eng.h, dptr(x), _i32p(lens), len(xs), dptr(out)))
+    return [wrap(o) for o in torch.split(out, [int(n) for n in lens])]
+
+
+def peak_normalize(y, device=None):
+    return peak_normalize_batch([y], device)[0]
+
+
+def _check_vad_envelope(window, width, silence):
+    if window < 1:
+        raise ValueError(f"vad: vad_window_length * sampling_rate // 1000 = {window} samples; a window needs at least one")
+    if window > TRIM_MAX_FRAME:
+        raise NotImplementedError(f"vad: a window of {window} samples; the engine's limit is {TRIM_MAX_FRAME}")
+    if int(width) != width or width < 1 or int(silence) != silence or silence < 0:
+        raise ValueError(f"vad: vad_moving_average_width = {width} must be a positive integer, vad_max_silence_length = "
+                         f"{silence} a non-negative one")
+    if width > TRIM_MAX_AVG:
+        raise NotImplementedError(f"vad: vad_moving_average_width = {width}; the engine's limit is {TRIM_MAX_AVG}")
+    if silence > TRIM_MAX_SILENCE:
+        raise NotImplementedError(f"vad: vad_max_silence_length = {silence}; the engine's limit is {TRIM_MAX_SILENCE}")
+
+
+def _vad_run(wavs, vad_window_length, vad_moving_average_width, vad_max_silence_length, sampling_rate, voice_flags=None,
+             vad_top_db=40, vad_floor_dBFS=-50, device=None, want_detector=False):
+    """-> (list of trimmed device tensors, kept windows per utterance, and with ``want_detector`` the window powers and the
+    voice flags the engine used, per utterance)."""
+    w = int(vad_window_length * sampling_rate) // 1000
+    _check_vad_envelope(w, vad_moving_average_width, vad_max_silence_length)
+    eng = _trim_engine(device)
+    ctx = eng.ctx
+    xs, lens, x = _pack(ctx, wavs, "trim_long_silences")
+    B = len(xs)
+    nw = [int(n) // w for n in lens]
+    total = sum(nw)
+    empty = lambda: wrap(ctx.empty((0,)))   # noqa: E731
+    if total == 0:
+        return ([empty() for _ in xs], np.zeros(B, np.int32), [ctx.empty((0,)) for _ in xs],
+                [torch.empty((0,), dtype=torch.bool, device=ctx.device) for _ in xs])
+    given = None
+    if voice_flags is not None:
+        voice_flags = list(voice_flags)
+        if len(voice_flags) != B:
+            raise ValueError(f"trim_long_silences: {len(voice_flags)} flag arrays for {B} signals")
+        fl = [ctx.to_device(np.asarray(f.cpu() if isinstance(f, torch.Tensor) else f).astype(bool).reshape(-1), torch.uint8)
+              for f in voice_flags]
+        for f, n in zip(fl, nw):
+            if f.numel() != n:
+                raise ValueError(f"trim_long_silences: {f.numel()} voice flags for a signal of {n} windows of {w} samples")
+        given = torch.cat(fl)
+    power = ctx.empty((total,)) if (want_detector and given is None) else None
+    flags = torch.empty((total,), dtype=torch.bool, device=x.device) if want_detector else None   # (bytes 0 / 1)
+    pos = torch.empty((total,), dtype=torch.int32, device=x.device)
+    kept = np.zeros(B, dtype=np.int32)
+    _capi.check(ctx.lib.pk_vad_mask(eng.h, dptr(x), _i32p(lens), B, w, int(vad_moving_average_width), int(vad_max_silence_length),
+                                    _vptr(given), 10.0 ** (-float(vad_top_db) / 10.0), 10.0 ** (float(vad_floor_dBFS) / 10.0),
+                                    _vptr(power), _vptr(flags), _vptr(pos), _i32p(kept)))
+    sizes = [int(k) * w for k in kept]
+    out = ctx.empty((sum(sizes),))
+    if sum(sizes):
+        _capi.check(ctx.lib.pk_vad_gather(eng.h, dptr(x), _i32p(lens), B, w, _vptr(pos), _i32p(kept), dptr(out)))
+    res = [wrap(o) for o in torch.split(out, sizes)]
+    if not want_detector:
+        return res, kept, None, None
+    return res, kept, None if power is None else list(torch.split(power, nw)), list(torch.split(flags, nw))
+
+
+def trim_long_silences_batch(wavs, vad_window_length, vad_moving_average_width, vad_max_silence_length, sampling_rate, *,
+                             voice_flags=None, vad_top_db=40, vad_floor_dBFS=-50, device=None):
+    """``trim_long_silences`` (examples/ge2e/audio_processor.py:53-107) for a ragged list -> a list of device tensors.
+
+    Windows of ``vad_window_length * sampling_rate // 1000`` samples (the tail is dropped), one voice flag per window, the
+    moving average of the flags rounded half to even, a dilation with ``ones(vad_max_silence_length + 1)``, and the samples of
+    the kept windows in order.  With ``voice_flags`` (one array per signal, from webrtcvad or anything else) everything runs
+    on the engine and is the reference's, exactly.  Without them the flags come from this project's energy detector, which is
+    NOT webrtcvad: window k is voiced iff its power exceeds both ``vad_top_db`` below the loudest window and
+    ``vad_floor_dBFS``.  The two defaults are design choices that nobody has compared with webrtcvad on speech, and an energy
+    detector flags loud noise as voice.  Two engine calls; the host reads the kept counts in between to size the result."""
+    return _vad_run(list(wavs), vad_window_length, vad_moving_average_width, vad_max_silence_length, sampling_rate,
+                    voice_flags, vad_top_db, vad_floor_dBFS, device)[0]
+
+
+def energy_voice_flags_batch(wavs, vad_window_length, sampling_rate, vad_top_db=40, vad_floor_dBFS=-50, device=None):
+    """What the energy detector (NOT webrtcvad) sees and decides: per signal ``(Q, flags)``, the power of every window
+    (float32) and its voice flag (bool), on the device."""
+    _, _, Q, flags = _vad_run(list(wavs), vad_window_length, 1, 0, sampling_rate, None, vad_top_db, vad_floor_dBFS, device,
+                              want_detector=True)
+    return [(wrap(q), f) for q, f in zip(Q, flags)]
+
+
+def trim_long_silences(wav, vad_window_length, vad_moving_average_width, vad_max_silence_length, sampling_rate, *,
+                       voice_flags=None, vad_top_db=40, vad_floor_dBFS=-50, device=None):
+    """One signal through ``trim_long_silences_batch``."""
+    return trim_long_silences_batch([wav], vad_window_length, vad_moving_average_width, vad_max_silence_length, sampling_rate,
+                                    voice_flags=None if voice_flags is None else [voice_flags], vad_top_db=vad_top_db,
+                                    vad_floor_dBFS=vad_floor_dBFS, device=device)[0]
+
+
 # ---- resampling ------------------------------------------------------------------------------------------------------
 # name -> (zeros, rolloff, beta): the number of zero crossings kept on each side (at the lower of the two rates), the cutoff as
 # a fraction of the lower Nyquist frequency, the Kaiser window's beta.  DESIGN.md 4.5d.

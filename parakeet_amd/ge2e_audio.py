@@ -6,8 +6,13 @@ padding, Slaney filters 0 .. sr / 2) computed by the engine's STFT / mel kernels
 partial batches stay on the device.
 
 Differences from the reference, both forced by what this package depends on:
-  * silence trimming needs ``webrtcvad``; without it the reference skips the step with a warning (:23-27, :217-220),
-    and so does this module, always (one warning per process);
+  * silence trimming (``trim_long_silences``, :53-107) needs ``webrtcvad``; without it the reference skips the step with a
+    warning (:23-27, :217-220), and so does this module by default (``vad=None``, one warning per process).  ``vad="energy"``
+    runs the step on the engine (``audio.trim_long_silences``) after ``normalize_volume``, as the reference
+    does at :217-220: everything after the voice detector is the reference's, but the detector is this project's energy
+    detector, NOT webrtcvad -- its two thresholds are design choices nobody has compared with webrtcvad on speech, and an
+    energy detector flags loud noise as voice.  ``vad=callable`` (``wav -> one flag per window``, e.g. a wrapper around
+    webrtcvad where it is installed) supplies the flags instead, and then the whole step is the reference's;
   * other sampling rates are resampled with ``scipy.signal.resample_poly`` on the host (``resampler="scipy"``, the default)
     or with the engine's polyphase kernel (``resampler="engine"``, ``audio.Resample``); neither is librosa's resampler.
 """
@@ -17,7 +22,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from .audio import _Engine, _resampler, load_wav, mel_filterbank
+from .audio import _Engine, _resampler, load_wav, mel_filterbank, trim_long_silences
 
 _VAD_WARNED = False
 
@@ -84,10 +89,13 @@ def resample(wav, source_sr, target_sr):
 class SpeakerVerificationPreprocessor:
     def __init__(self, sampling_rate, audio_norm_target_dBFS, vad_window_length, vad_moving_average_width,
                  vad_max_silence_length, mel_window_length, mel_window_step, n_mels, partial_n_frames,
-                 min_pad_coverage=0.75, partial_overlap_ratio=0.5, device=None, resampler="scipy"):
+                 min_pad_coverage=0.75, partial_overlap_ratio=0.5, device=None, resampler="scipy", vad=None):
         if resampler not in ("scipy", "engine"):
             raise ValueError(f"resampler must be 'scipy' or 'engine', got {resampler!r}")
+        if not (vad is None or vad == "energy" or callable(vad)):
+            raise ValueError(f"vad must be None, 'energy' or a callable wav -> voice flags, got {vad!r}")
         self.resampler = resampler
+        self.vad = vad
         self.sampling_rate = sampling_rate
         self.audio_norm_target_dBFS = audio_norm_target_dBFS
         self.vad_window_length = vad_window_length
@@ -119,8 +127,22 @@ class SpeakerVerificationPreprocessor:
             else:
                 wav = resample(wav, source_sr, self.sampling_rate)
         wav = normalize_volume(wav, self.audio_norm_target_dBFS, increase_only=True)
-        _warn_no_vad()
-        return wav
+        if self.vad is None:
+            _warn_no_vad()
+            return wav
+        return self.trim_long_silences(wav)
+
+    def trim_long_silences(self, wav):
+        """The reference's step (:53-107) with this preprocessor's VAD parameters, on the engine -> float32 numpy.  The voice
+        flags come from the energy detector (``vad="energy"``, NOT webrtcvad) or from the callable, which gets the wav cut to
+        whole windows, as the reference hands it to its detector."""
+        wav = np.asarray(wav, dtype=np.float32)
+        flags = None
+        if callable(self.vad):
+            w = (self.vad_window_length * self.sampling_rate) // 1000
+            flags = self.vad(wav[:len(wav) - len(wav) % w])
+        return trim_long_silences(wav, self.vad_window_length, self.vad_moving_average_width, self.vad_max_silence_length,
+                                  self.sampling_rate, voice_flags=flags, device=self._device).cpu().numpy()
 
     def melspectrogram(self, wav):
         """(frames, n_mels) float32 power mel on the device."""
@@ -151,9 +173,9 @@ class SpeakerVerificationPreprocessor:
         return out
 
 
-def ge2e_preprocessor(overlap=0.5, device=None, resampler="scipy"):
+def ge2e_preprocessor(overlap=0.5, device=None, resampler="scipy", vad=None):
     """The released configuration (examples/ge2e/config.py): 16 kHz, -30 dBFS, 25 ms / 10 ms windows, 40 mels,
     160-frame partials, min_pad_coverage 0.75.  examples/ge2e/inference.py passes ``partial_overlap_ratio =
     min_pad_coverage`` (:81): use overlap=0.75 to reproduce its corpus embeddings; the class default is 0.5."""
     return SpeakerVerificationPreprocessor(16000, -30, 30, 8, 6, 25, 10, 40, 160, min_pad_coverage=0.75,
-                                           partial_overlap_ratio=overlap, device=device, resampler=resampler)
+                                           partial_overlap_ratio=overlap, device=device, resampler=resampler, vad=vad)
