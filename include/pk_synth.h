@@ -1018,6 +1018,41 @@ int pk_guided_attn_run(pk_ctx* ctx, const float* att, const int64_t* offs, int64
                        const int32_t* maps, const int32_t* rows, const int32_t* cols, int32_t B, double sigma, double* sums_out,
                        int32_t flags);
 
+/* --------------------------------------- durations from a teacher's attention */
+/* Monotonic alignment search (the best monotonic path through a score matrix, the dynamic programme of Glow-TTS's
+ * maximum_path) and the focus rate of attention maps (FastSpeech, 3.3) for ragged batches (csrc/align.hip).
+ * The definition is this project's own (csrc/pk_align.h states it in full); it is NOT the Montreal Forced Aligner.  Data
+ * pointers are DEVICE pointers; offs, rows, cols, maps are HOST arrays; offsets and strides count floats.  An utterance's
+ * results are the same bits alone, in any batch and at any position in it; its neighbours in a packed buffer are never read.
+ *
+ * pk_mas_run: utterance b is rows[b] (decoder steps S) x cols[b] (tokens T) entries, row s at scores_or_att + offs[b] +
+ * s * row_stride.  offs NULL: the utterances follow one another (row_stride must be 0); row_stride 0 means cols[b]; a padded
+ * (B, Smax, Tmax) tensor is offs[b] = b * Smax * Tmax, row_stride = Tmax.  mode 0: the entries are the scores v; mode 1: they
+ * are attention weights A and v = logf(A < eps ? eps : A) (eps > 0 and finite).  Q(0, 0) = v(0, 0), Q(s, t) = v(s, t) +
+ * max(Q(s - 1, t), Q(s - 1, t - 1)) in float64 for t <= s, -inf otherwise; the path ends in (S - 1, T - 1) and at row s >= 1
+ * stays in its column t iff Q(s - 1, t) >= Q(s - 1, t - 1).
+ *   durations_out  packed int32, sum cols: rows of the path per token, each >= 1, summing to rows[b];
+ *   path_out       NULL, or packed int32, sum rows: the path's column at every row;
+ *   score_out      NULL, or (B) double: Q(S - 1, T - 1);
+ *   status_out     NULL, or (B) int32: 1 if a v(s, t) with t <= s is not finite (that utterance's durations and path are then
+ *                  unspecified), else 0;
+ *   scores_out     NULL, or (mode 1 only) packed float, sum rows * cols, contiguous: the v the search used.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): cols <= 1024, rows <= 16384.
+ * PK_EINVAL: NULL ctx / input / rows / cols / durations_out, B <= 0, an empty utterance, cols[b] > rows[b], a stride below
+ * the columns, an unknown mode, eps that is not positive and finite. */
+int pk_mas_run(pk_ctx* ctx, const float* scores_or_att, const int64_t* offs, int64_t row_stride, const int32_t* rows,
+               const int32_t* cols, int32_t B, int32_t mode, float eps, int32_t* durations_out, int32_t* path_out,
+               double* score_out, int32_t* status_out, float* scores_out);
+/* The 32-bit decision words of an utterance that stay in LDS; an utterance has rows * 2 * ceil(cols / 64) of them and keeps
+ * them in a global workspace when that is more. */
+int pk_mas_lds_words(int32_t* words);
+/* Focus rate F = (1 / S) sum_s max_t A[s, t] of every map; the layout is pk_guided_attn_run's (utterance b owns maps[b]
+ * maps of rows[b] x cols[b], map g's row s at att + offs[b] + g * map_stride + s * row_stride; zero strides and NULL
+ * offsets as there).  The maximum is exact, the sum float64 in the fixed order csrc/pk_align.h states.  rates_out: packed
+ * double, sum maps.  PK_EINVAL as for pk_guided_attn_run; PK_EUNSUPPORTED: more than 2^30 maps in a call. */
+int pk_focus_rate_run(pk_ctx* ctx, const float* att, const int64_t* offs, int64_t map_stride, int64_t row_stride,
+                      const int32_t* maps, const int32_t* rows, const int32_t* cols, int32_t B, double* rates_out);
+
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).
  * Replaces the paddle.randn calls of PWGGenerator.inference (parallel_wavegan.py:515-516) and

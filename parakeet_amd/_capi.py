@@ -308,6 +308,10 @@ def _declare(lib):
         "pk_pair_loss_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i64, i64, i32p, i32, i32, C.c_void_p, i32]),
         "pk_bce_logits_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i32p, i32, C.c_float, C.c_void_p, i32]),
         "pk_guided_attn_run": (C.c_int, [vp, f32p, i64p, i64, i64, i32p, i32p, i32p, i32, C.c_double, C.c_void_p, i32]),
+        "pk_mas_run": (C.c_int, [vp, f32p, i64p, i64, i32p, i32p, i32, i32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, f32p]),
+        "pk_mas_lds_words": (C.c_int, [i32p]),
+        "pk_focus_rate_run": (C.c_int, [vp, f32p, i64p, i64, i64, i32p, i32p, i32p, i32, C.c_void_p]),
         "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),

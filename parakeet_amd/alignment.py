@@ -1,0 +1,252 @@
+"""Durations from a teacher's attention: monotonic alignment search and focus rate on the HIP engine.
+
+``monotonic_align`` is the best monotonic path through a score matrix (the dynamic programme of Glow-TTS's ``maximum_path``)
+for ragged batches, ``durations_from_attention`` the same on ``log(max(A, eps))`` of attention maps with the post-step a
+FastSpeech recipe needs, ``focus_rate`` / ``select_map`` FastSpeech's criterion for choosing a head, ``write_durations`` the
+``utt|speaker|ph d ph d ...`` file examples/fastspeech2_features.py reads.  The definition is this project's own
+(csrc/pk_align.h); these are a teacher's attention boundaries, NOT the Montreal Forced Aligner's forced alignment.  Maps that
+are device tensors stay on the device: views of one packed tensor (what ``teacher_forced_batch`` returns) are addressed
+in place.  Rows are decoder steps S, columns tokens T."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _capi
+from .runtime import Context, dptr, wrap
+
+__all__ = ["monotonic_align", "durations_from_attention", "focus_rate", "select_map", "write_durations", "MAX_TOKENS",
+           "MAX_ROWS"]
+
+MAX_TOKENS, MAX_ROWS = 1024, 16384        # csrc/pk_align.h: MAS_MAX_COLS, MAS_MAX_ROWS
+
+
+def _is_map(x):
+    return isinstance(x, (np.ndarray, torch.Tensor)) or (hasattr(x, "numpy") and hasattr(x, "shape"))
+
+
+def _lengths(x, B, what):
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().as_subclass(torch.Tensor).numpy()
+    x = np.asarray(x).reshape(-1).astype(np.int64)
+    if x.size != B:
+        raise ValueError(f"{B} utterances, {x.size} {what}")
+    return x
+
+
+def _layout(x, rows, cols, lead):
+    """The accepted forms -> (maps, rows, cols, G, lead_shape, single, padded).  ``lead``: the number of leading map
+    dimensions an utterance may have (0 for the search, up to 2 for the focus rate).  maps: a list of per-utterance arrays /
+    tensors, or the one padded tensor."""
+    if (rows is None) != (cols is None):
+        raise ValueError("rows and cols go together: the valid lengths of a padded (B, ..., Smax, Tmax) tensor")
+    if rows is not None:
+        if not _is_map(x) or not 3 <= len(x.shape) <= 3 + lead:
+            raise ValueError("rows / cols describe one padded tensor of shape (B, Smax, Tmax)" +
+                             (" or (B, ..., Smax, Tmax)" if lead else "") + f", got {type(x).__name__}"
+                             + (f" of shape {tuple(x.shape)}" if _is_map(x) else ""))
+        B = int(x.shape[0])
+        if B == 0:
+            raise ValueError("no utterances given")
+        r, c = _lengths(rows, B, "row counts"), _lengths(cols, B, "column counts")
+        if (r < 1).any() or (c < 1).any() or (r > x.shape[-2]).any() or (c > x.shape[-1]).any():
+            raise ValueError(f"lengths {r.tolist()} x {c.tolist()} do not lie in 1 ... {int(x.shape[-2])} x {int(x.shape[-1])}")
+        ls = tuple(int(v) for v in x.shape[1:-2])
+        return x, r, c, int(np.prod(ls, dtype=np.int64)), ls, False, True
+    single = _is_map(x)
+    maps = [x] if single else list(x)
+    if not maps:
+        raise ValueError("no utterances given")
+    ls = None
+    for b, m in enumerate(maps):
+        if not _is_map(m) or not 2 <= len(m.shape) <= 2 + lead:
+            raise ValueError(f"utterance {b}: expected a map of shape " + ("(..., S, T)" if lead else "(S, T)") +
+                             (f", got shape {tuple(m.shape)}" if _is_map(m) else f", got {type(m).__name__}"))
+        if min(m.shape) < 1:
+            raise ValueError(f"utterance {b} is empty: shape {tuple(m.shape)}")
+        l = tuple(int(v) for v in m.shape[:-2])
+        if ls is not None and l != ls:
+            raise ValueError(f"utterance {b} has maps {l}, utterance 0 has {ls}")
+        ls = l
+    r = np.array([m.shape[-2] for m in maps], dtype=np.int64)
+    c = np.array([m.shape[-1] for m in maps], dtype=np.int64)
+    return maps, r, c, int(np.prod(ls, dtype=np.int64)), ls, single, False
+
+
+def _check_envelope(r, c):
+    for b in range(r.size):
+        if c[b] > r[b]:
+            raise ValueError(f"utterance {b} has more tokens ({int(c[b])}) than rows ({int(r[b])}): no monotonic path gives "
+                             "every token a row")
+    for b in range(r.size):
+        if c[b] > MAX_TOKENS:
+            raise NotImplementedError(f"utterance {b} has {int(c[b])} tokens; the engine's envelope is 1 ... {MAX_TOKENS}")
+        if r[b] > MAX_ROWS:
+            raise NotImplementedError(f"utterance {b} has {int(r[b])} rows; the engine's envelope is 1 ... {MAX_ROWS}")
+
+
+def _device_ok(t, ctx):
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == ctx.device and t.dtype == torch.float32
+            and t.is_contiguous())
+
+
+def _place(ctx, maps, r, c, G, padded):
+    """-> (keep, pointer, offs (B,) int64, map_stride, row_stride): where the engine finds the maps.  Nothing is copied when
+    the maps are float32 views of one device tensor (or one padded device tensor); anything else is packed by one device
+    concatenation (device tensors) or one upload (host arrays)."""
+    B = r.size
+    if padded:
+        t = maps if _device_ok(maps, ctx) else ctx.to_device(maps)
+        Sm, Tm = int(t.shape[-2]), int(t.shape[-1])
+        return t, dptr(t), np.arange(B, dtype=np.int64) * (G * Sm * Tm), Sm * Tm, Tm
+    if all(_device_ok(m, ctx) for m in maps):
+        ts = [m.as_subclass(torch.Tensor) for m in maps]
+        if len({t.untyped_storage().data_ptr() for t in ts}) == 1:
+            base = min(t.data_ptr() for t in ts)
+            return ts, C.c_void_p(base), np.array([(t.data_ptr() - base) // 4 for t in ts], dtype=np.int64), 0, 0
+        flat = torch.cat([t.reshape(-1) for t in ts])
+    elif all(isinstance(m, torch.Tensor) and m.is_cuda for m in maps):
+        flat = torch.cat([m.as_subclass(torch.Tensor).to(device=ctx.device, dtype=torch.float32).reshape(-1) for m in maps])
+    else:
+        host = [m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else (np.asarray(m.numpy()) if hasattr(m, "numpy")
+                                                                             and not isinstance(m, np.ndarray) else m)
+                for m in maps]
+        flat = ctx.to_device(np.concatenate([np.asarray(h, dtype=np.float32).reshape(-1) for h in host]))
+    offs = np.concatenate(([0], np.cumsum(G * r * c)[:-1])).astype(np.int64)
+    return flat, dptr(flat), offs, 0, 0
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _p(a, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _run(x, rows, cols, mode, eps, return_path, return_v):
+    maps, r, c, _, _, single, padded = _layout(x, rows, cols, 0)
+    _check_envelope(r, c)
+    ctx = Context.get()
+    keep, ptr, offs, _, row_stride = _place(ctx, maps, r, c, 1, padded)
+    B = int(r.size)
+    r32, c32 = _i32(r), _i32(c)
+    dur = ctx.empty((int(c.sum()),), dtype=torch.int32)
+    path = ctx.empty((int(r.sum()),), dtype=torch.int32) if return_path else None
+    score = ctx.empty((B,), dtype=torch.float64)
+    status = ctx.empty((B,), dtype=torch.int32)
+    v = ctx.empty((int((r * c).sum()),)) if return_v else None
+    _capi.check(ctx.lib.pk_mas_run(ctx.handle, ptr, _p(offs, C.c_int64), int(row_stride), _p(r32, C.c_int32), _p(c32, C.c_int32),
+                                   B, int(mode), float(eps), dptr(dur), None if path is None else dptr(path), dptr(score),
+                                   dptr(status), None if v is None else dptr(v)))
+    st = status.cpu().numpy()
+    del keep
+    if st.any():
+        bad = [int(b) for b in np.flatnonzero(st)]
+        raise FloatingPointError(f"monotonic alignment: utterance(s) {bad} hold a score that is not finite in a reachable cell "
+                                 "(column <= row)")
+    d, sc = dur.cpu().numpy(), score.cpu().numpy()
+    p = path.cpu().numpy() if return_path else None
+    co, ro, vo = np.concatenate(([0], np.cumsum(c))), np.concatenate(([0], np.cumsum(r))), np.concatenate(([0], np.cumsum(r * c)))
+    durs = [d[co[b]:co[b + 1]].copy() for b in range(B)]
+    paths = [p[ro[b]:ro[b + 1]].copy() for b in range(B)] if return_path else None
+    vs = [wrap(v[vo[b]:vo[b + 1]].view(int(r[b]), int(c[b]))) for b in range(B)] if return_v else None
+    return single, durs, sc, paths, vs
+
+
+def monotonic_align(scores, rows=None, cols=None, *, return_path=False):
+    """Monotonic alignment search (``pk_mas_run``, scores mode).  ``scores``: one (S, T) map, a list of (S_b, T_b) maps, or a
+    padded (B, Smax, Tmax) tensor with ``rows`` / ``cols`` (B,), the valid lengths; float32, numpy or tensors on any device.
+    Returns ``(durations, score)`` or, with ``return_path``, ``(durations, score, path)``: per utterance the int32 numpy
+    durations (T_b,) (each >= 1, sum S_b), the float64 path score Q(S - 1, T - 1) and the int32 numpy path (S_b,) -- lists
+    (and a (B,) float64 array) for a list or a padded tensor, the bare items for one 2-D map.  ValueError names the utterance
+    with more tokens than rows; NotImplementedError outside 1 <= T <= 1024, S <= 16384; FloatingPointError when a score in a
+    reachable cell (column <= row) is not finite."""
+    single, durs, sc, paths, _ = _run(scores, rows, cols, 0, 0.0, return_path, False)
+    out = (durs[0], float(sc[0])) if single else (durs, sc)
+    if return_path:
+        out += (paths[0] if single else paths,)
+    return out
+
+
+def durations_from_attention(att, rows=None, cols=None, *, eps=1e-8, reduction_factor=1, merge_last=False,
+                             return_scores=False):
+    """Durations of attention maps (``pk_mas_run``, attention mode: the search on ``logf(max(A, eps))`` formed on the device).
+    ``att`` as ``scores`` of ``monotonic_align``.  ``merge_last``: the last column's rows go to the column before it and the
+    column is dropped (the <eos> column of a TransformerTTS map; needs T >= 2); ``reduction_factor`` multiplies the counts (a
+    TransformerTTS decoder step is r frames).  Returns ``(durations, score)`` and, with ``return_scores``, the (S_b, T_b) device
+    tensors of the scores the search used as a third item."""
+    r = int(reduction_factor)
+    if r < 1:
+        raise ValueError(f"reduction_factor {reduction_factor} must be a positive integer")
+    if not (float(eps) > 0.0 and np.isfinite(np.float32(eps)) and np.float32(eps) > 0):
+        raise ValueError(f"eps {eps} must be a positive float32 number")
+    if merge_last:
+        c = _layout(att, rows, cols, 0)[2]
+        if (c < 2).any():
+            raise ValueError(f"merge_last needs at least two columns; utterance {int(np.flatnonzero(c < 2)[0])} has one")
+    single, durs, sc, _, vs = _run(att, rows, cols, 1, eps, False, return_scores)
+    durs = [_post(d, r, merge_last) for d in durs]
+    out = (durs[0], float(sc[0])) if single else (durs, sc)
+    if return_scores:
+        out += (vs[0] if single else vs,)
+    return out
+
+
+def _post(d, r, merge_last):
+    if merge_last:
+        d = d.copy()
+        d[-2] += d[-1]
+        d = d[:-1]
+    return (d * np.int32(r)).astype(np.int32)
+
+
+def focus_rate(att, rows=None, cols=None):
+    """FastSpeech's focus rate F = (1 / S) sum_s max_t A[s, t] of every map (``pk_focus_rate_run``).  ``att``: one utterance's
+    maps (S, T), (G, S, T) or (layers, heads, S, T); a list of such (the same leading shape for all); or a padded
+    (B, ..., Smax, Tmax) tensor with ``rows`` / ``cols``.  Returns float64 numpy of the leading shape per utterance (a list for
+    a list or a padded tensor)."""
+    maps, r, c, G, ls, single, padded = _layout(att, rows, cols, 2)
+    ctx = Context.get()
+    keep, ptr, offs, map_stride, row_stride = _place(ctx, maps, r, c, G, padded)
+    B = int(r.size)
+    out = ctx.empty((B * G,), dtype=torch.float64)
+    g32, r32, c32 = np.full(B, G, dtype=np.int32), _i32(r), _i32(c)
+    _capi.check(ctx.lib.pk_focus_rate_run(ctx.handle, ptr, _p(offs, C.c_int64), int(map_stride), int(row_stride),
+                                          _p(g32, C.c_int32), _p(r32, C.c_int32), _p(c32, C.c_int32), B, dptr(out)))
+    f = out.cpu().numpy().reshape((B,) + ls)
+    del keep
+    return f[0] if single else [f[b] for b in range(B)]
+
+
+def select_map(att, rows=None, cols=None):
+    """The index of the map with the largest focus rate per utterance (the first of equal ones): a tuple over the leading
+    dimensions, ``(layer, head)`` for TransformerTTS's (dlayers, aheads, S, T + 1) maps."""
+    f = focus_rate(att, rows, cols)
+    pick = lambda a: tuple(int(i) for i in np.unravel_index(int(np.argmax(a)), a.shape))  # noqa: E731
+    return [pick(a) for a in f] if isinstance(f, list) else pick(np.asarray(f))
+
+
+def write_durations(path, utt_ids, speakers, phones, durations):
+    """One ``utt|speaker|ph d ph d ...`` line per utterance (d in frames), the file ``read_durations`` of
+    examples/fastspeech2_features.py reads.  ``speakers``: one name per utterance, or one name for all."""
+    utt_ids = [str(u) for u in utt_ids]
+    if isinstance(speakers, str):
+        speakers = [speakers] * len(utt_ids)
+    if not (len(utt_ids) == len(speakers) == len(phones) == len(durations)):
+        raise ValueError(f"{len(utt_ids)} utterances, {len(speakers)} speakers, {len(phones)} phone lists, {len(durations)} duration lists")
+    lines = []
+    for u, spk, ph, d in zip(utt_ids, speakers, phones, durations):
+        ph, d = [str(p) for p in ph], [int(v) for v in np.asarray(d).reshape(-1)]
+        if len(ph) != len(d):
+            raise ValueError(f"{u}: {len(ph)} phones, {len(d)} durations")
+        if not ph:
+            raise ValueError(f"{u}: no phones")
+        for s in [u, str(spk)] + ph:
+            if "|" in s or any(ch.isspace() for ch in s) or not s:
+                raise ValueError(f"{u}: {s!r} cannot be written: names hold no '|' and no white space")
+        if min(d) < 0:
+            raise ValueError(f"{u}: a negative duration")
+        lines.append(f"{u}|{spk}|" + " ".join(f"{p} {v}" for p, v in zip(ph, d)))
+    with open(path, "wt", encoding="utf-8") as f:
+        f.write("".join(line + "\n" for line in lines))

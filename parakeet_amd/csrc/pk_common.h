@@ -148,6 +148,8 @@ struct pk_ctx_scratch {
     pk_dbuf seq_tab;     // seq_loss.hip: the same three for pk_pair_loss_run, pk_bce_logits_run, pk_guided_attn_run
     pk_dbuf seq_part;
     pk_dbuf seq_io;
+    pk_dbuf mas_tab;     // align.hip: the call's table of pk_mas_run / pk_focus_rate_run, the decision words that do not fit LDS
+    pk_dbuf mas_bits;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

@@ -88,6 +88,8 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->seq_tab.release();
         kv.second->seq_part.release();
         kv.second->seq_io.release();
+        kv.second->mas_tab.release();
+        kv.second->mas_bits.release();
         delete kv.second;
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -173,6 +173,19 @@ class Tacotron2:
                                             flens.ctypes.data_as(i32p), seeds_p, flags, frames.ctypes.data_as(i32p)))
         return self._read(ctx, lens, frames)
 
+    def durations_batch(self, texts, mels, tones=None, seeds=None, global_condition=None, return_focus=False):
+        """Token durations from the teacher-forced attention: ``teacher_forced_batch`` with these arguments,
+        then ``alignment.durations_from_attention`` on its (L_b, T_b) alignments, which never leave the device.  Returns
+        ``(durations, score)``: a list of (T_b,) int32 numpy arrays, each entry >= 1 and each array summing to L_b, and the (B,)
+        float64 path scores (the sum of log attention along the path); with ``return_focus`` also the (B,) float64 focus
+        rates of the alignments (``alignment.focus_rate``).  Needs T_b <= L_b.  These are the attention's boundaries, not a
+        forced aligner's."""
+        from .alignment import durations_from_attention, focus_rate
+        outs = self.teacher_forced_batch(texts, mels, tones=tones, seeds=seeds, global_condition=global_condition)
+        maps = [o["alignments"] for o in outs]
+        res = durations_from_attention(maps)
+        return res + (np.array([float(f) for f in focus_rate(maps)]),) if return_focus else res
+
     def forward(self, text_inputs, text_lens, mels, output_lens=None, tones=None, global_condition=None, seed=0):
         """``Tacotron2.forward`` (:691-778) with eval semantics (like ``infer``: only the prenet's dropout is live, stream
         ``seed + b`` for utterance b): text_inputs (B, T_text) padded ids, text_lens (B,), mels (B, T_mel, d_mels) padded,

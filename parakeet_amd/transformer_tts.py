@@ -271,6 +271,30 @@ class TransformerTTS:
             o += L
         return outs
 
+    def durations_batch(self, texts, speech, seeds=None, spembs=None, map="focus", return_focus=False):
+        """Token durations from the teacher-forced encoder-decoder attention: ``teacher_forced_batch``, one
+        (layer, head) map per utterance -- ``map="focus"``: the one with the largest focus rate (``alignment.select_map``), or
+        a ``(layer, head)`` pair for all --, then ``alignment.durations_from_attention`` on it with the <eos> column merged into
+        the last token and the counts multiplied by ``reduction_factor``.  The maps never leave the device.  Returns
+        ``(durations, score)``: a list of (T_b,) int32 numpy arrays summing to (L_b // r) * r frames, and the (B,) float64 path
+        scores (with ``return_focus`` also the (B,) float64 focus rates of the maps used); the maps used are kept as
+        ``last_maps``, a list of (layer, head).  Needs T_b + 1 <= L_b // r."""
+        from .alignment import durations_from_attention, focus_rate, select_map
+        if not (isinstance(map, str) and map == "focus"):
+            try:
+                layer, head = (int(v) for v in map)
+            except (TypeError, ValueError):
+                raise ValueError(f'map must be "focus" or a (layer, head) pair, got {map!r}') from None
+            if not (0 <= layer < self._dlayers and 0 <= head < self._aheads):
+                raise ValueError(f"map ({layer}, {head}) outside the model's {self._dlayers} layers x {self._aheads} heads")
+        outs = self.teacher_forced_batch(texts, speech, seeds=seeds, spembs=spembs, return_att=True)
+        atts = [a for _, a in outs]
+        picks = select_map(atts) if isinstance(map, str) else [(layer, head)] * len(atts)
+        self.last_maps = picks
+        used = [a[l, h] for a, (l, h) in zip(atts, picks)]
+        res = durations_from_attention(used, reduction_factor=self.reduction_factor, merge_last=True)
+        return res + (np.array([float(f) for f in focus_rate(used)]),) if return_focus else res
+
     def _read_teacher(self):
         """Packed ``before_outs`` (sum frames, odim) and stop ``logits`` (sum frames,) of the last ``teacher_forced_batch``."""
         ctx = Context.get(self._ctx.device)

@@ -216,6 +216,14 @@ inline void poison_lds(void* p, size_t bytes) {
 }
 // rendezvous of the live lanes of the wave (build.py puts it where a "// [wave-lds-exchange]" marker stands)
 inline void wave_sync() { arrive(&cur->wave->rv); }
+// the mask of the live lanes whose predicate holds (the slots of lanes that are not live are not looked at)
+inline unsigned long long ballot(int pred) {
+    const int live = cur->wave->rv.live;
+    const int p = exchange(pred);
+    unsigned long long m = 0;
+    for (int i = 0; i < live; ++i) m |= (unsigned long long)(peek<int>(p, i) != 0) << i;
+    return m;
+}
 inline int readlane(int v, int lane) {
     const int p = exchange(v);
     return peek<int>(p, lane);
@@ -272,6 +280,15 @@ template <class T> static inline T __shfl_up(T v, int d, int width = 64) { retur
 // ---------------------------------------------------------------------------------------------- scalar intrinsics
 static inline int __float_as_int(float f) { int i; std::memcpy(&i, &f, 4); return i; }
 static inline unsigned __float_as_uint(float f) { unsigned i; std::memcpy(&i, &f, 4); return i; }
+static inline int __double2loint(double d) { long long i; std::memcpy(&i, &d, 8); return (int)(i & 0xffffffffll); }
+static inline int __double2hiint(double d) { long long i; std::memcpy(&i, &d, 8); return (int)(i >> 32); }
+static inline double __hiloint2double(int hi, int lo) {
+    const unsigned long long i = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+    double d;
+    std::memcpy(&d, &i, 8);
+    return d;
+}
+#define __ballot(pred) hipemu::ballot((pred) ? 1 : 0)
 static inline float __int_as_float(int i) { float f; std::memcpy(&f, &i, 4); return f; }
 static inline float __uint_as_float(unsigned i) { float f; std::memcpy(&f, &i, 4); return f; }
 #define __expf(x) std::exp((float)(x))     // glibc declares __expf / __logf itself

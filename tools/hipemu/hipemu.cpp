@@ -200,6 +200,8 @@ int update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bou
         from = in_row - (ctrl & 15) >= 0 ? l - (ctrl & 15) : -1;               // row_shr
     else if (ctrl >= 0x121 && ctrl <= 0x12f)
         from = (l & ~15) | ((in_row - (ctrl & 15)) & 15);                      // row_ror
+    else if (ctrl == 0x138)
+        from = l >= 1 ? l - 1 : -1;                                            // wave_shr:1 (align.hip)
     else if (ctrl == 0x140)
         from = (l & ~15) | (15 - in_row);                                      // row_mirror
     else if (ctrl == 0x141)
