@@ -12,7 +12,9 @@ fmin, fmax, f0min, f0max``.  Written under ``--output-dir``: ``data_speech/<utt>
 ``data_pitch/<utt>_pitch.npy`` and ``data_energy/<utt>_energy.npy`` (T, 1), and ``metadata.jsonl`` with the keys
 examples/fastspeech2_gta.py reads (``utt_id, phones, durations, pitch, energy, feats``; ``text`` with ``--phones-dict``,
 ``spk_id`` with ``--speaker-dict``).  With ``--speech-stats / --pitch-stats / --energy-stats`` (the (2, dim) mean / scale
-files of compute_statistics.py) the features are written normalised, as normalize.py leaves them.
+files of compute_statistics.py) the features are written normalised, as normalize.py leaves them.  ``--write-stats DIR``
+saves ``speech_stats.npy``, ``pitch_stats.npy`` and ``energy_stats.npy`` of the raw (not normalised) features just extracted,
+from the device tensors (parakeet_amd.normalizer.FeatureStats).
 
 The pitch is this project's estimator (parakeet_amd.audio.Pitch), NOT pyworld's DIO + StoneMask, which the
 reference calls; the wav loader's resampler is the project's own too (4.5d).  All utterances run as one ragged batch through
@@ -121,6 +123,12 @@ def extract(args):
               for e, d in zip(energy_extractor.get_energy_batch([wavs[i] for i in keep]), durs)]
     for sub in ("data_speech", "data_pitch", "data_energy"):
         os.makedirs(os.path.join(args.output_dir, sub), exist_ok=True)
+    if args.write_stats is not None:
+        from parakeet_amd.normalizer import FeatureStats
+        os.makedirs(args.write_stats, exist_ok=True)
+        for kind, xs in (("speech", [mels[i] for i in keep]), ("pitch", pitch), ("energy", energy)):
+            if xs:
+                FeatureStats(xs[0].shape[1]).fit(xs).save(os.path.join(args.write_stats, f"{kind}_stats.npy"))
     records = []
     for i, d, f0, en in zip(keep, durs, pitch, energy):
         utt = utts[i]
@@ -159,6 +167,8 @@ def parse_args(argv=None):
     ap.add_argument("--speech-stats", default=None)
     ap.add_argument("--pitch-stats", default=None)
     ap.add_argument("--energy-stats", default=None)
+    ap.add_argument("--write-stats", default=None, metavar="DIR",
+                    help="save speech_stats.npy, pitch_stats.npy and energy_stats.npy of the raw features here")
     return ap.parse_args(argv)
 
 

@@ -1053,6 +1053,35 @@ int pk_mas_lds_words(int32_t* words);
 int pk_focus_rate_run(pk_ctx* ctx, const float* att, const int64_t* offs, int64_t map_stride, int64_t row_stride,
                       const int32_t* maps, const int32_t* rows, const int32_t* cols, int32_t B, double* rates_out);
 
+/* ------------------------------------------------------- feature statistics */
+/* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
+ * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature
+ * dimension D with the state
+ *   n (int64 rows), K (D float32, the shift), S1[c] = sum (x[r, c] - K[c]), S2[c] = sum (x[r, c] - K[c])^2 (float64).
+ * K is fixed once: the shift given to pk_stats_reset, else the first row the accumulator ever sees.  Differences, squares
+ * and additions are single IEEE float64 operations in THE ORDER csrc/pk_stats.h states (row tiles anchored at the
+ * utterance's first row, a fixed lane map, a fixed tree; utterances added left to right): an utterance's sums are the same
+ * bytes alone and in any batch, a corpus gives the same state bytes in any split into updates at utterance boundaries.  No
+ * atomics.  NaN and Inf propagate.  mean = K + S1 / n, var = max(S2 - S1^2 / n, 0) / n are formed by the caller.
+ * Envelope (else PK_EUNSUPPORTED, before any launch): 1 <= D <= 1024; lens[b] <= 2^31 - 1; at most 2^24 tiles per update.
+ * PK_EINVAL: NULL handle / lens, B <= 0, a negative length, NULL rows with rows to read, unknown flags. */
+typedef struct pk_stats pk_stats;
+#define PK_STATS_MOMENTS_ONLY 1   /* pk_stats_update: write moments_out only; n, K, S1, S2 stay (PK_ESTATE while K is open) */
+int pk_stats_create(pk_ctx* ctx, int32_t D, pk_stats** out);
+void pk_stats_destroy(pk_stats* h);
+/* n = 0, S1 = S2 = 0; shift (HOST, D floats) fixes K, NULL leaves it open for the first row.  Synchronises. */
+int pk_stats_reset(pk_stats* h, const float* shift);
+/* Rows per tile for dimension D (HOST out); tiles start at utterance-relative multiples of it. */
+int pk_stats_tile_rows(int32_t D, int32_t* rows);
+/* rows: DEVICE, packed (sum lens, D) float32, utterance after utterance.  lens: HOST (B) int64; 0 is allowed and adds
+ * nothing.  moments_out: NULL, or DEVICE (B, 2 D) float64: utterance b's S1 | S2 about K.  The state becomes
+ * S + U_0 + U_1 + ... + U_{B-1}, added in that order.  Three launches, no read-back. */
+int pk_stats_update(pk_stats* h, const float* rows, const int64_t* lens, int32_t B, double* moments_out, int32_t flags);
+/* The state through HOST buffers (any may be NULL): n, have_shift (0 while K is open), shift (D floats), s1, s2 (D doubles
+ * each).  pk_stats_get synchronises the stream first; pk_stats_set with shift NULL (only with n = 0) leaves K open. */
+int pk_stats_get(pk_stats* h, int64_t* n, int32_t* have_shift, float* shift, double* s1, double* s2);
+int pk_stats_set(pk_stats* h, int64_t n, const float* shift, const double* s1, const double* s2);
+
 /* ------------------------------------------------------------ normal noise */
 /* Standard-normal floats on the device: out[i] for i in [0, n), a pure function of (seed, offset + i).
  * Replaces the paddle.randn calls of PWGGenerator.inference (parallel_wavegan.py:515-516) and

@@ -30,6 +30,8 @@ PK_SEQ_LOSS_PAIR_TILE, PK_SEQ_LOSS_GUIDE_ROWS, PK_SEQ_LOSS_GUIDE_COLS, PK_SEQ_LO
 # csrc/pk_trim.h: windows per scan step of the VAD mask kernel; the pad modes of pk_trim_run
 PK_TRIM_SCAN_CHUNK = 256
 PK_TRIM_PAD = {None: 0, "reflect": 1, "constant": 2}
+# csrc/pk_stats.h: the envelope of pk_stats_*; pk_stats_update's flag
+PK_STATS_MAX_DIM, PK_STATS_MAX_ROWS, PK_STATS_MOMENTS_ONLY = 1024, 2 ** 31 - 1, 1
 _EXC = {
     -1: ValueError,
     -2: AssertionError,
@@ -312,7 +314,14 @@ def _declare(lib):
                                  C.c_void_p, f32p]),
         "pk_mas_lds_words": (C.c_int, [i32p]),
         "pk_focus_rate_run": (C.c_int, [vp, f32p, i64p, i64, i64, i32p, i32p, i32p, i32, C.c_void_p]),
-        "pk_op_average_by_duration": (C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
+        "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
+        "pk_stats_destroy": (None, [vp]),
+        "pk_stats_reset": (C.c_int, [vp, f32p]),
+        "pk_stats_tile_rows": (C.c_int, [i32, i32p]),
+        "pk_stats_update": (C.c_int, [vp, f32p, i64p, i32, C.c_void_p, i32]),
+        "pk_stats_get": (C.c_int, [vp, i64p, i32p, f32p, C.c_void_p, C.c_void_p]),
+        "pk_stats_set": (C.c_int, [vp, i64, f32p, C.c_void_p, C.c_void_p]),
+        "pk_op_average_by_duration":(C.c_int, [vp, f32p, i64, i32, i64p, i32, f32p]),
         "pk_op_expand": (C.c_int, [vp, f32p, i64p, i32, i32, i32, i32, f32p]),
         "pk_op_sinusoid_position_encoding": (C.c_int, [vp, i32, i32, C.c_float, i32, f32p]),
         "pk_op_scaled_dot_product_attention": (C.c_int, [vp, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32,
