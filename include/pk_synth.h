@@ -177,6 +177,12 @@ int pk_pwg_set_chunk_samples(pk_pwg* h, int64_t samples);
  *                  pk_pwg_finalize -- no first_conv launch, no x planes for layer 0 (round 6); 0 = first_conv, then the ordinary first block.
  *                  Both are within the engine's error bars of the reference; they differ from each other in the last bits.
  *   "scale_guard_every"  the sampling period under "scale_guard" 1 (default 16; 0 = never re-sample).
+ *   "fused_tail"   1 (default) = on the "planes" path at hop 256 (default math, layers >= 2, one chunk) the last residual block of a call that
+ *                  is neither guarded nor sampled computes the waveform itself: last_conv_layers run on the skip sum in the block's registers,
+ *                  the block's x_out and the finished skip sum are not stored and the separate last-layers launch is gone.  Same bits as
+ *                  0 (= the ordinary last block, then the last-layers kernel).  pk_pwg_debug_read of taps 1, 2, 3 after a fused call first
+ *                  runs the ordinary last block once on the handle's stream (its inputs are still in the workspace), so the taps are
+ *                  those of 0 too.  No effect on the generic path.
  *   "generic_kernel"  1 = run the default shape on the shape-generic kernels as well (pwg_gen.hip; other shapes always
  *                  do); 0 (default) = the tuned kernels.  Takes effect at the next pk_pwg_finalize.  On the generic path
  *                  x is fp32 with a measured scale per 32-sample block under both split maths (the "planes" = 0 scheme):

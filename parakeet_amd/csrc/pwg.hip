@@ -436,6 +436,9 @@ struct PwgLayerArgs {
     float nz_wmax, nz_bmax;  // NZ: max|w|, max|b| of first_conv (the B operand is built from wmax n and bmax)
     long noise_n;            // NZ: floats in noise (index clamp)
     unsigned* amax_out;      // PL + AMAX (guarded / sampled calls): [B][PWG_AMAX_PARTS] bits of max|xout| per utterance, folded in by the epilogue
+    float* wav;              // LAST (fused tail): the packed waveform, and last_conv_layers' scalars as k_pwg_last_h3 takes them in PwgLastArgs
+    float last_scale, last_b2;   // sqrt(1 / layers), last_conv_layers.3.bias
+    int last_kw;             // the tail's W fragments hold last_conv_layers.1.weight * 2^last_kw
     PwgGen gen;              // GEN kernels only (hop != 256)
 };
 
@@ -868,13 +871,22 @@ __device__ __forceinline__ void split_x8s(const float (&v)[8], float s, f16x8& h
 // utterance, u = sum_c W1[co][c][tap] w[c], v = sum_c W1[co][c][tap] b[c] folded in fp64 by pk_pwg_finalize.  Stage 1's 12 k-steps become ONE (the six
 // "channels" n(t-1), n(t), n(t+1) and the three in-utterance flags): 12 MFMAs instead of 144, no plane reads (768 B/sample), no k_pwg_first launch (1.34 GB
 // written); the residual input w n + b is recomputed.  hop 256, planes path only.
-template <bool FIRST, bool HALF, int ABL = 0, bool GEN = false, bool PL = false, bool AMAX = false, bool NZ = false>
+// LAST ("fused tail"): the last block of the stack on the planes path at hop 256, when nobody reads its x_out.  Pass 0 of stage 2 (conv1x1_out, the
+// residual add, the scale-and-split and the plane stores) is not run; the finished skip sum is not stored either: acc2[q][r] of the skip pass IS
+// k_pwg_last_h3's operand sv[ks][e] (q = ks >> 1, r = 8 (ks & 1) + e), so last_conv_layers follow in the same registers, step for step as k_pwg_last_h3<false>
+// does them (the waveform has the same bits), and a wave stores 4 B per sample.  The host gives this launch its own W2 image -- the fragments of
+// last_conv_layers.1 in the two co-tile slots of conv1x1_out -- and its own bias image [conv bias G | last_conv_layers.1.bias | skip bias | last_conv_layers.3
+// weight]: 64 floats more of LDS than the ordinary block.  pk_pwg_debug_read replays the ordinary block when somebody does ask for x_out or the skip sum.
+template <bool FIRST, bool HALF, int ABL = 0, bool GEN = false, bool PL = false, bool AMAX = false, bool NZ = false, bool LAST = false>
 __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer_b3(PwgLayerArgs a) {
     static_assert(!NZ || (FIRST && PL && !GEN), "noise-fed: the first block of the planes path at hop 256");
     static_assert(!PL || (HALF && ABL == 0), "planes: the block-scaled split-fp16 path only");
+    static_assert(!LAST || (HALF && PL && !GEN && !FIRST && !AMAX && !NZ && ABL == 0 && PK_PWG_SKIP_VEC != 0),
+                  "fused tail: an ordinary planes block at hop 256 whose skip sum is in accumulator order");
     typedef typename Split16<HALF>::vec bf16x8;     // shadows the bf16 typedef inside this kernel
     typedef typename Split16<HALF>::elem elem16;
-    __shared__ __attribute__((aligned(16))) float lds[GEN ? LDS_TOTAL_GEN : LDS_TOTAL];
+    constexpr int N_BIAS = LDS_BIAS + (LAST ? SK : 0);
+    __shared__ __attribute__((aligned(16))) float lds[(GEN ? LDS_TOTAL_GEN : LDS_TOTAL) + (LAST ? SK : 0)];
     float* lds_bias = lds + LDS_W1 + LDS_W2;
     {
         const f32x4* src = reinterpret_cast<const f32x4*>(NZ ? a.nz_tab : a.w1);
@@ -884,8 +896,10 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         f32x4* dst2 = reinterpret_cast<f32x4*>(lds + LDS_W1);
         for (int i = threadIdx.x; i < B3_W2_BYTES / 16; i += LAYER_WAVES * 64) dst2[i] = src2[i];
         if (threadIdx.x < LDS_BIAS) lds_bias[threadIdx.x] = a.bias[threadIdx.x];
+        else if (threadIdx.x < N_BIAS) lds[LDS_TOTAL + (threadIdx.x - LDS_BIAS)] = a.bias[threadIdx.x];   // LAST: behind the waves' P rows
     }
     __syncthreads();
+    [[maybe_unused]] const float* lds_l2w = lds + LDS_TOTAL;   // LAST: last_conv_layers.3.weight [SK]
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1088,7 +1102,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         int utt_v = 0;  // PL + AMAX: the tile's utterance
         if constexpr (PL) {
             kxn_v = a.tile_kx_in[next_wt >> 3];
-            ko_v = a.tile_kx_out[wt >> 3];
+            if constexpr (!LAST) ko_v = a.tile_kx_out[wt >> 3];
             if constexpr (AMAX) utt_v = a.gen.tile_utt[wt >> 3];   // requested here like ko_v: a load in the epilogue would wait for every prefetched operand
             xs_cur = __uint_as_float(0x3f3504f3u - ((unsigned)kx << 23));   // sqrt(0.5) * 2^-kx
         }
@@ -1229,7 +1243,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
                 } else {
                     split_x8<bf16x8, elem16, HALF>(ring[(g + 1) % B3_RING], nh, nl);
                 }
-                if (g1 % 3 == 1) {   // centre tap: these fp32 values are x_in at this lane's output rows
+                if (!LAST && g1 % 3 == 1) {   // centre tap: these fp32 values are x_in at this lane's output rows
 #pragma unroll
                     for (int e = 0; e < 8; ++e)
                         x_old[16 * ((g1 / 3) >> 1) + 8 * ((g1 / 3) & 1) + e] = ring[(g + 1) % B3_RING][e];
@@ -1295,8 +1309,109 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         };
 #pragma unroll
         for (int slot = 0; slot < 5; ++slot) gate_piece(0, slot);
-        bf16x8 f_ah = lds_a2[0], f_al = lds_a2[4 * 64];
+        bf16x8 f_ah = lds_a2[(LAST ? 2 : 0) * 64], f_al = lds_a2[(4 + (LAST ? 2 : 0)) * 64];   // LAST starts with the skip co-tiles (2, 3)
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (LAST) {
+            // the skip sum through block layers - 2 (x_old's registers are free in this instantiation: requested before the first MFMA)
+#pragma unroll
+            for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 t = pwg_skip_ld4((a.skip + (8 * qq + 2 * r4) * 128) + svo);
+                    sk_old[16 * qq + 4 * r4 + 0] = t[0];
+                    sk_old[16 * qq + 4 * r4 + 1] = t[1];
+                    sk_old[16 * qq + 4 * r4 + 2] = t[2];
+                    sk_old[16 * qq + 4 * r4 + 3] = t[3];
+                }
+            f32x16 acc2[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias + G + 64 + 32 * q + 8 * r4 + 4 * hi);
+                    acc2[q][4 * r4 + 0] = bv[0];
+                    acc2[q][4 * r4 + 1] = bv[1];
+                    acc2[q][4 * r4 + 2] = bv[2];
+                    acc2[q][4 * r4 + 3] = bv[3];
+                }
+            __builtin_amdgcn_sched_barrier(0);
+            // the skip pass (pass 1 of the ordinary block: same MFMAs in the same order), with the gate of k-step ks + 1 under the MFMAs of k-step ks
+            // as pass 0 has it there: every gate_piece(ks + 1, .) stands before the first MFMA that reads zh / zl[ks + 1]
+#pragma unroll
+            for (int idx = 0; idx < 2 * B3_KS2; ++idx) {
+                const int ks = idx >> 1, q = idx & 1;
+                const int nidx = idx + 1 < 2 * B3_KS2 ? idx + 1 : idx;
+                const int nks = nidx >> 1, nq = nidx & 1;
+                acc2[q] = mfma16(f_ah, zh[ks], acc2[q]);
+                const bf16x8 n_ah = lds_a2[((nks * 2 + 0) * 4 + 2 + nq) * 64];
+                const bf16x8 n_al = lds_a2[((nks * 2 + 1) * 4 + 2 + nq) * 64];
+                __builtin_amdgcn_sched_barrier(0);
+                gate_piece(ks + 1, 3 * q + 0);
+                __builtin_amdgcn_sched_barrier(0);
+                acc2[q] = mfma16(f_al, zh[ks], acc2[q]);
+                __builtin_amdgcn_sched_barrier(0);
+                gate_piece(ks + 1, 3 * q + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                acc2[q] = mfma16(f_ah, zl[ks], acc2[q]);
+                __builtin_amdgcn_sched_barrier(0);
+                gate_piece(ks + 1, 3 * q + 2);
+                __builtin_amdgcn_sched_barrier(0);
+                f_ah = n_ah;
+                f_al = n_al;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // last_conv_layers on the finished sum, as k_pwg_last_h3<false> does them: ReLU(sum * sqrt(1 / layers)), the wave's block scale, the
+            // 64 -> 64 conv as three-term split-fp16 sums from b1 * S, ReLU, the dot with last_conv_layers.3
+            float sv[B3_KS2][8];
+            float am = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < B3_KS2; ++ks)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int q = ks >> 1, r = 8 * (ks & 1) + e;
+                    const float v = fmaf(acc2[q][r], a.i1, sk_old[16 * q + r]);   // the skip sum of all blocks: never stored
+                    sv[ks][e] = fmaxf(v * a.last_scale, 0.f);
+                    am = fmaxf(am, sv[ks][e]);
+                }
+            am = wave_max64(am);
+            const int kl = blk_scale_exp((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(am)));
+            const float sl = pow2f(kl), Sl = pow2f(kl + a.last_kw), Sl_inv = pow2f(-(kl + a.last_kw));
+            f32x16 acc3[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias + G + 32 * q + 8 * r4 + 4 * hi);   // last_conv_layers.1.bias
+                    acc3[q][4 * r4 + 0] = bv[0] * Sl;
+                    acc3[q][4 * r4 + 1] = bv[1] * Sl;
+                    acc3[q][4 * r4 + 2] = bv[2] * Sl;
+                    acc3[q][4 * r4 + 3] = bv[3] * Sl;
+                }
+#pragma unroll
+            for (int ks = 0; ks < B3_KS2; ++ks) {
+                bf16x8 bh, bl;
+                split_x8s(sv[ks], sl, bh, bl);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const bf16x8 ah = lds_a2[((ks * 2 + 0) * 4 + q) * 64];   // last_conv_layers.1 in the co-tile slots of conv1x1_out
+                    const bf16x8 al = lds_a2[((ks * 2 + 1) * 4 + q) * 64];
+                    acc3[q] = mfma16(ah, bh, acc3[q]);
+                    acc3[q] = mfma16(al, bh, acc3[q]);
+                    acc3[q] = mfma16(ah, bl, acc3[q]);
+                }
+            }
+            float part = 0.f;
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x4 wv = *reinterpret_cast<const f32x4*>(lds_l2w + 32 * q + 8 * r4 + 4 * hi);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) part = fmaf(wv[i], fmaxf(acc3[q][4 * r4 + i], 0.f), part);   // ReLU commutes with S > 0
+                }
+            part += __shfl_xor(part, 32);
+            if (hi == 0) a.wav[(long)(wt >> 3) * TILE + (wt & 7) * WAVE_T + j] = fmaf(part, Sl_inv, a.last_b2);
+        } else {
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
             f32x16 acc2[2];
@@ -1459,6 +1574,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
                 }
             }
         }
+        }   // !LAST
         kx = kx_next;
         if constexpr (NZ) cls_cur = cls_next;
     }
@@ -1666,6 +1782,15 @@ struct pk_pwg {
     bool planes_on = true;     // x as pre-split fp16 planes under the split-fp16 math (k_pwg_layer_b3<..., PL>); PK_PWG_PLANES=0: off
     bool last_planes = false;  // ... and whether the last run used them (debug tap 1 decodes)
     bool last_skip_vec = false;   // the last run left the skip sum in accumulator order (PK_PWG_SKIP_VEC: the split kernels; debug tap 2 decodes)
+    // "fused_tail": the last block of an unguarded, unsampled call on the planes path at hop 256 is k_pwg_layer_b3's LAST instantiation, which emits the
+    // waveform (no k_pwg_last_h3 launch).  Such a call leaves neither the last block's x_out nor the finished skip sum behind: the handle keeps the ordinary
+    // launch's arguments, and pk_pwg_debug_read replays that one block (its inputs are all still in the workspace) before it reads tap 1, 2 or 3.
+    bool fused_tail = true;
+    bool tail_pending = false;    // the last inference was fused and its last block has not been replayed
+    PwgLayerArgs tail_args;       // ... the ordinary last block of that inference
+    pk_dbuf d_w2_tail, d_bias_tail;   // LAST's images: W2 with last_conv_layers.1 in conv1x1_out's co-tile slots; [conv bias | l1 bias | skip bias | l3 weight]
+    std::vector<uint16_t> tail_w2_host;   // (pk_pwg_finalize: the last block's fp16 W2 fragments and scaled bias on their way into those images)
+    std::vector<float> tail_bias_host;
     // "scale_guard": 0 off, 1 the first inference after finalize, 2 every inference.  A guarded inference on the planes path
     // measures max|x| per utterance and layer (k_pwg_planes_amax) and compares with the a-priori bound of k_pwg_tile_scales
     int scale_guard = 1;
@@ -1858,6 +1983,9 @@ extern "C" int pk_pwg_set_option(pk_pwg* h, const char* key, int64_t value) {
     } else if (strcmp(key, "noise_fed_first") == 0) {
         if (value < 0 || value > 1) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: noise_fed_first %lld (0, 1)", (long long)value);
         h->noise_fed = value != 0;
+    } else if (strcmp(key, "fused_tail") == 0) {
+        if (value < 0 || value > 1) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: fused_tail %lld (0, 1)", (long long)value);
+        h->fused_tail = value != 0;
     } else if (strcmp(key, "generic_kernel") == 0) {
         if (value < 0 || value > 1) PK_FAIL(PK_EINVAL, "pk_pwg_set_option: generic_kernel %lld (0, 1)", (long long)value);
         h->generic_opt = value != 0;
@@ -2175,6 +2303,7 @@ extern "C" int pk_pwg_finalize(pk_pwg* h) {
                                 a2[((((size_t)ks * 2 + 1) * 4 + q) * 64 + lane) * 8 + e] = bl;
                             }
             }
+            if (half) h->tail_w2_host.assign(W2b.end() - n2b, W2b.end());
             PK_TRY(pk_upload(ctx, half ? h->d_w1h : h->d_w1b, W1b.data(), W1b.size() * sizeof(uint16_t)));
             PK_TRY(pk_upload(ctx, half ? h->d_w2h : h->d_w2b, W2b.data(), W2b.size() * sizeof(uint16_t)));
         }
@@ -2195,6 +2324,7 @@ extern "C" int pk_pwg_finalize(pk_pwg* h) {
                 for (int i = 0; i < SK; ++i) bb[G + R + i] = std::ldexp(bb[G + R + i], 14 + h->k2s[l]);
             }
             PK_TRY(pk_upload(ctx, h->d_bias_h, Bh.data(), Bh.size() * sizeof(float)));
+            h->tail_bias_host.assign(Bh.end() - nb, Bh.end());
         }
         std::vector<float> packed;
         pk_gemm_pack(Wa.data(), AUX, c.layers * G, packed);
@@ -2231,6 +2361,21 @@ extern "C" int pk_pwg_finalize(pk_pwg* h) {
                             Ah[((((size_t)ks * 2 + 1) * 2 + q) * 64 + lane) * 8 + e] = bl;
                         }
             PK_TRY(pk_upload(ctx, h->d_l1h, Ah.data(), Ah.size() * sizeof(uint16_t)));
+            // the fused tail's images (k_pwg_layer_b3, LAST): the last block's W2 with these fragments in the co-tile slots 0, 1 of conv1x1_out, and its
+            // bias with last_conv_layers.1.bias in conv1x1_out's place and last_conv_layers.3.weight behind
+            std::vector<uint16_t>& W2t = h->tail_w2_host;
+            for (int ks = 0; ks < 4; ++ks)
+                for (int part = 0; part < 2; ++part)
+                    for (int q = 0; q < 2; ++q)
+                        memcpy(W2t.data() + (((size_t)ks * 2 + part) * 4 + q) * 64 * 8, Ah.data() + (((size_t)ks * 2 + part) * 2 + q) * 64 * 8, 64 * 8 * sizeof(uint16_t));
+            std::vector<float>& Bt = h->tail_bias_host;
+            for (int i = 0; i < SK; ++i) Bt[G + i] = b1[i];
+            Bt.insert(Bt.end(), w2.begin(), w2.begin() + SK);
+            PK_TRY(pk_upload(ctx, h->d_w2_tail, W2t.data(), W2t.size() * sizeof(uint16_t)));
+            PK_TRY(pk_upload(ctx, h->d_bias_tail, Bt.data(), Bt.size() * sizeof(float)));
+            W2t.clear();
+            Bt.clear();
+            h->tail_pending = false;   // (a replay would run on the new weights)
         }
         PK_TRY(pk_upload(ctx, h->d_l1b, b1.data(), SK * sizeof(float)));
         PK_TRY(pk_upload(ctx, h->d_l2, w2.data(), SK * sizeof(float)));
@@ -2272,6 +2417,7 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
         return pwg_gen_infer(h->gen, k, mel, frames, B, noise, wav, flags);
     }
     pwg_poll_sample(h, false);   // the verdict of an earlier sampled call, if its copies have landed (never waits)
+    h->tail_pending = false;
     const pk_pwg_cfg& c = h->cfg;
     const int hop = h->hop, gap = h->gap;
     // ---- layout.  Utterances start on 256-sample boundaries (work tiles are 256-sample chunks of an utterance;
@@ -2484,6 +2630,7 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
         amax = h->ws_amax.as<unsigned>();
         PK_HIP(hipMemsetAsync(amax, 0, n_amax * sizeof(unsigned), ctx->stream));
     }
+    bool fused = false;   // this call's last block emitted the waveform
     for (int attempt = 0;; ++attempt) {
     bool amax_parts_used = false;   // AMAX layer kernels ran: their parts are folded into amax[] behind the stack
     h->last_planes = planes;
@@ -2501,6 +2648,11 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
     }
     // noise-fed first block (k_pwg_layer_b3's NZ): no first_conv launch, no x planes for layer 0 -- hop 256 on the planes path
     const bool nz = planes && !gen && !all_first && h->noise_fed && h->d_nz.p != nullptr;
+    // fused tail (k_pwg_layer_b3's LAST): the last block emits the waveform.  Not on a guarded or sampled call (they need max|x_out| of the last block),
+    // not under a measurement switch, and not on a chunked call (kept on the ordinary path: one configuration less to hold against the goldens)
+    const bool fuse = h->fused_tail && planes && !gen && !guard && !sample && h->dbg == 0 && c.layers >= 2 && h->math == PK_PWG_MATH_F16X3 &&
+                      (long)sumS <= h->chunk_samples && h->d_w2_tail.p != nullptr;
+    fused = fuse;
     if (nz) {
     } else if (planes && gen)
         PK_LAUNCH(ctx, "pwg_first", (k_pwg_first<true, true>), dim3(sumC), dim3(TILE), 0, d_noise, h->d_first_w.as<float>(),
@@ -2549,6 +2701,9 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
             a.nz_tab = nullptr;
             a.noise_n = 0;
             a.nz_wmax = a.nz_bmax = 0.f;
+            a.wav = nullptr;
+            a.last_scale = a.last_b2 = 0.f;
+            a.last_kw = 0;
             a.xin = (l & 1) ? h->ws_x1.as<float>() : h->ws_x0.as<float>();
             a.xout = (l & 1) ? h->ws_x0.as<float>() : h->ws_x1.as<float>();
             a.skip = h->ws_skip.as<float>();
@@ -2611,6 +2766,16 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
                         else PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, true, true>), dim3(grid), blk, 0, a);
                     } else if (nz && l == 0) {
                         PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<true, true, 0, false, true, false, true>), dim3(grid), blk, 0, a);
+                    } else if (fuse && l == c.layers - 1) {
+                        h->tail_args = a;        // what pk_pwg_debug_read replays for taps 1, 2, 3
+                        h->tail_pending = true;
+                        a.w2 = reinterpret_cast<const float*>(h->d_w2_tail.as<char>());
+                        a.bias = h->d_bias_tail.as<float>();
+                        a.wav = d_wav;
+                        a.last_scale = (float)std::sqrt(1.0 / c.layers);
+                        a.last_b2 = h->l2_bias;
+                        a.last_kw = h->kw_last;
+                        PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, false, true, false, false, true>), dim3(grid), blk, 0, a);
                     } else {
                         if (l == 0 || all_first) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<true, true, 0, false, true>), dim3(grid), blk, 0, a);
                         else PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, false, true>), dim3(grid), blk, 0, a);
@@ -2673,7 +2838,7 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
     }
     }
     // ---- last layers
-    {
+    if (!fused) {
         PwgLastArgs a;
         a.skip = h->ws_skip.as<float>();
         a.w1 = h->d_l1.as<float>();
@@ -2724,6 +2889,12 @@ extern "C" int pk_pwg_debug_read(pk_pwg* h, int32_t what, int32_t b, float* host
         PK_HIP(hipStreamSynchronize(ctx->stream));
         PK_HIP(hipMemcpy(host_out, h->ws_dbg.p, (size_t)G * S * 4, hipMemcpyDeviceToHost));
         return PK_OK;
+    }
+    if (h->tail_pending && what >= 1 && what <= 3) {
+        // the last inference's last block emitted the waveform (fused tail): its x_out and the finished skip sum exist only once the ordinary block has
+        // run -- x_in, the skip sum through block layers - 2, P and the tables are where that inference left them
+        h->tail_pending = false;
+        PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, false, true>), dim3(ctx->n_cu), dim3(LAYER_WAVES * 64), 0, h->tail_args);
     }
     if (what == 3 && h->last_planes) PK_FAIL(PK_EUNSUPPORTED, "pk_pwg_debug_read: the planes path keeps no block maxima");
     if (what == 3) {
@@ -2796,7 +2967,7 @@ extern "C" void pk_pwg_destroy(pk_pwg* h) {
     (void)hipStreamSynchronize(h->ctx->stream);
     pk_dbuf* bufs[] = {&h->d_first_w, &h->d_first_b, &h->d_convin_wT, &h->d_uptab, &h->d_mu, &h->d_sigma,
                        &h->d_w1, &h->d_w2, &h->d_bias, &h->d_w1b, &h->d_w2b, &h->d_w1h, &h->d_w2h, &h->d_waux, &h->d_nz, &h->d_l1, &h->d_l1h, &h->d_l1b, &h->d_l2,
-                       &h->d_bias_h, &h->ws_xe0, &h->ws_xe1,
+                       &h->d_bias_h, &h->d_w2_tail, &h->d_bias_tail, &h->ws_xe0, &h->ws_xe1,
                        &h->ws_mel, &h->ws_cin, &h->ws_noise, &h->ws_wav, &h->ws_c0, &h->ws_P,
                        &h->ws_x0, &h->ws_x1, &h->ws_skip, &h->ws_dbg, &h->ws_tab, &h->d_cl, &h->ws_nmax, &h->ws_tkx, &h->ws_amax};
     for (auto* b : bufs) b->release();
