@@ -834,6 +834,43 @@ int pk_pitch_tile_frames(pk_pitch* h, int32_t* tile);
  * flags: PK_HOST_IO if wav and the outputs are host pointers (then synchronous). */
 int pk_pitch_run(pk_pitch* h, const float* wav, const int32_t* lens, int32_t B, float* f0_out, int32_t* lag_out,
                  float* cmnd_out, int32_t flags);
+/* A second decision stage behind the same d': Viterbi tracking over per-frame candidates ("Viterbi tracking over
+ * candidates"; this project's own design, like the estimator).  pk_pitch_run's results are not touched by it.
+ *   candidates of a frame: the lags tau in [tau_min, tau_max - 1] with d'(tau) < d'(tau - 1), d'(tau) <= d'(tau + 1) and
+ *     d'(tau) < theta_c (fp32 comparisons); the K smallest by (d', tau) are kept and stored by ascending tau, an empty slot
+ *     has lag 0 and cost +inf
+ *   states of a frame: the K slots (observation cost: d' of the slot, as float64) and "unvoiced" (unvoiced_cost)
+ *   transitions: slot to slot lambda * |T[tau_s] - T[tau_p]|, T a float64 table of log2(tau) made on the host; unvoiced to
+ *     unvoiced 0; voiced to unvoiced or back switch_cost
+ *   D_0[s] = obs_0[s];  D_i[s] = min_p (D_(i-1)[p] + tr(p, s)) + obs_i[s] in float64, added in that order, the product not
+ *     contracted into the sum; a tie goes to the smaller p (unvoiced is the last state), slots of cost +inf are skipped; the
+ *     path ends in the smallest s of minimal D, which is the score; a frame's lag is its state's, 0 for unvoiced, and f0 is
+ *     refined as pk_pitch_run refines it.
+ * PK_EINVAL: K outside 1 ... 8, a threshold that is not a number, a cost that is negative, infinite or not a number. */
+typedef struct {
+    int32_t K;               /* candidates kept per frame */
+    float theta_c;           /* candidate threshold */
+    double lambda;           /* cost of one octave between consecutive voiced frames */
+    double unvoiced_cost;    /* observation cost of the unvoiced state (parakeet_amd.audio.Pitch passes its threshold) */
+    double switch_cost;      /* voiced <-> unvoiced */
+} pk_pitch_track_cfg;
+/* wav, lens, B, flags: as pk_pitch_run.  Every output may be NULL; packed by utterance: f0_out one float and lag_out one int32
+ * per frame (0 for an unvoiced frame), score_out one double per utterance, cand_lag_out / cand_cost_out K values per frame.
+ * An utterance's results are bit-identical alone, in any batch and at any position in it.
+ * PK_EINVAL: NULL h / wav / lens / cfg, B <= 0, an empty utterance, and the configuration's (above).
+ * PK_EUNSUPPORTED: an utterance of more than 2^22 frames. */
+int pk_pitch_track_run(pk_pitch* h, const float* wav, const int32_t* lens, int32_t B, const pk_pitch_track_cfg* cfg, float* f0_out,
+                       int32_t* lag_out, double* score_out, int32_t* cand_lag_out, float* cand_cost_out, int32_t flags);
+/* The same on d' rows of the caller: cmnd holds tau_max + 1 floats per frame, packed by track; frames (B, host) >= 1 each.
+ * Rows that pk_pitch_run wrote give what pk_pitch_track_run gives, bit for bit.  Values in the rows that are not numbers are
+ * never candidates; negative values order as numbers do.  PK_EINVAL / PK_EUNSUPPORTED as above (an empty track: PK_EINVAL). */
+int pk_pitch_track_from_cmnd(pk_pitch* h, const float* cmnd, const int32_t* frames, int32_t B, const pk_pitch_track_cfg* cfg,
+                             float* f0_out, int32_t* lag_out, double* score_out, int32_t* cand_lag_out, float* cand_cost_out,
+                             int32_t flags);
+/* Named integer options (results do not change):
+ *   "track_lds_frames"  1 ... 4096 (default 4096): tracks of more frames keep the tracker's backpointers in a global workspace,
+ *                       not in LDS */
+int pk_pitch_set_option(pk_pitch* h, const char* key, int64_t value);
 void pk_pitch_destroy(pk_pitch* h);
 /* Pitch._convert_to_continuous_f0 (get_feats.py:99-119) and the log step of _calculate_f0 (:136-138) for B packed f0
  * tracks, from any estimator: frames before the first / after the last non-zero value take that value, a zero frame i

@@ -117,6 +117,11 @@ class PitchCfg(C.Structure):
                 ("threshold", C.c_float)]
 
 
+class PitchTrackCfg(C.Structure):
+    _fields_ = [("K", C.c_int32), ("theta_c", C.c_float), ("lambda_", C.c_double), ("unvoiced_cost", C.c_double),
+                ("switch_cost", C.c_double)]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -281,6 +286,11 @@ def _declare(lib):
         "pk_pitch_frames": (C.c_int, [vp, i64, i32p]),
         "pk_pitch_tile_frames": (C.c_int, [vp, i32p]),
         "pk_pitch_run": (C.c_int, [vp, f32p, i32p, i32, f32p, C.c_void_p, f32p, i32]),
+        "pk_pitch_track_run": (C.c_int, [vp, f32p, i32p, i32, C.POINTER(PitchTrackCfg), f32p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, i32]),
+        "pk_pitch_track_from_cmnd": (C.c_int, [vp, f32p, i32p, i32, C.POINTER(PitchTrackCfg), f32p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, i32]),
+        "pk_pitch_set_option": (C.c_int, [vp, cstr, i64]),
         "pk_pitch_destroy": (None, [vp]),
         "pk_op_continuous_f0": (C.c_int, [vp, f32p, i32p, i32, i32, f32p]),
         "pk_trim_create": (C.c_int, [vp, C.POINTER(vp)]),

@@ -355,6 +355,8 @@ class Energy:
 # ---- pitch -----------------------------------------------------------------------------------------------------------
 # the engine's envelope (csrc/pk_pitch.h)
 PITCH_MAX_TAU, PITCH_MAX_HOP = 960, 16384
+PITCH_MAX_CANDIDATES, PITCH_MAX_TRACK_FRAMES, PITCH_TRACK_LDS_FRAMES = 8, 1 << 22, 4096
+PITCH_TRACKERS = ("frame", "viterbi")
 
 
 def pitch_lags(sr, f0min, f0max):
@@ -411,10 +413,32 @@ class Pitch:
     defined in DESIGN.md 4.5e (YIN's difference function, cumulative-mean normalisation, absolute ``threshold`` and
     parabolic refinement; csrc/pitch.hip), which returns f0 in Hz on the same frame grid (``len(wav) // hop_length + 1``
     frames) with its own voicing decisions.  Everything after the estimator is the reference's: continuous f0, the log of the
-    non-zero values, token averages.  Results are device tensors, as ``Energy`` returns them."""
+    non-zero values, token averages.  Results are device tensors, as ``Energy`` returns them.
 
-    def __init__(self, sr=24000, hop_length=300, f0min=80, f0max=7600, *, threshold=0.1, win_length=None, device=None):
+    ``tracker="frame"`` (the default) decides every frame on its own.  ``tracker="viterbi"`` puts a second decision stage behind
+    the same d': up to ``max_candidates`` (1 ... 8) local minima of d' under ``candidate_threshold`` per frame, and the cheapest
+    path over them with ``octave_cost`` per octave between consecutive voiced frames, ``unvoiced_cost`` (default: ``threshold``)
+    per unvoiced frame and ``switch_cost`` per change of voicing (this project's own design too; checked on
+    synthetic signals only).  ``track``, ``_calculate_f0``, ``get_pitch`` and ``get_pitch_batch`` follow the handle's tracker."""
+
+    def __init__(self, sr=24000, hop_length=300, f0min=80, f0max=7600, *, threshold=0.1, win_length=None, device=None,
+                 tracker="frame", max_candidates=8, candidate_threshold=0.5, octave_cost=1.0, unvoiced_cost=None,
+                 switch_cost=0.05):
         self.sr, self.hop_length, self.f0min, self.f0max = sr, hop_length, f0min, f0max
+        if tracker not in PITCH_TRACKERS:
+            raise ValueError(f"pitch: tracker = {tracker!r}; one of {PITCH_TRACKERS}")
+        if int(max_candidates) != max_candidates or not 1 <= max_candidates <= PITCH_MAX_CANDIDATES:
+            raise ValueError(f"pitch: max_candidates = {max_candidates} must be an integer in 1 ... {PITCH_MAX_CANDIDATES}")
+        if candidate_threshold != candidate_threshold:
+            raise ValueError("pitch: candidate_threshold is not a number")
+        costs = dict(octave_cost=octave_cost, switch_cost=switch_cost,
+                     unvoiced_cost=threshold if unvoiced_cost is None else unvoiced_cost)
+        for name, v in costs.items():
+            if not (0 <= v < math.inf):
+                raise ValueError(f"pitch: {name} = {v} must be a finite number >= 0")
+        self.tracker, self.max_candidates, self.candidate_threshold = tracker, int(max_candidates), float(candidate_threshold)
+        self.octave_cost, self.switch_cost, self.unvoiced_cost = (float(costs[k]) for k in ("octave_cost", "switch_cost",
+                                                                                            "unvoiced_cost"))
         self.tau_min, self.tau_max = pitch_lags(sr, f0min, f0max)
         if int(sr) != sr or int(hop_length) != hop_length or hop_length < 1:
             raise ValueError(f"pitch: sr = {sr} and hop_length = {hop_length} must be positive integers")
@@ -467,9 +491,85 @@ class Pitch:
         return split(f0), split(lag), split(cm)
 
     def track(self, wavs):
-        """Ragged list -> per utterance ``(f0_raw, lag)``: (frames,) float32 Hz (0 for unvoiced) and int32 lags (0)."""
+        """Ragged list -> per utterance ``(f0_raw, lag)``: (frames,) float32 Hz (0 for unvoiced) and int32 lags (0), decided by the
+        handle's ``tracker``."""
+        if self.tracker == "viterbi":
+            return self.track_viterbi(wavs)
         f0, lag, _ = self._run(list(wavs), want_lag=True)
         return [(wrap(a), b) for a, b in zip(f0, lag)]
+
+    # ---- Viterbi tracking over candidates (DESIGN.md 4.5e)
+    def set_track_lds_frames(self, n):
+        """Tracks of more than ``n`` frames (1 ... 4096, the default) keep the tracker's backpointers in a global workspace
+        instead of LDS.  The results do not change."""
+        if int(n) != n or not 1 <= n <= PITCH_TRACK_LDS_FRAMES:
+            raise ValueError(f"pitch: track_lds_frames = {n} must be an integer in 1 ... {PITCH_TRACK_LDS_FRAMES}")
+        _capi.check(self.ctx.lib.pk_pitch_set_option(self.h, b"track_lds_frames", int(n)))
+
+    def _track_cfg(self):
+        return _capi.PitchTrackCfg(self.max_candidates, self.candidate_threshold, self.octave_cost, self.unvoiced_cost,
+                                   self.switch_cost)
+
+    def _track_outputs(self, ctx, nf, want_cand):
+        total, K = sum(nf), self.max_candidates
+        f0 = ctx.empty((total,))
+        lag = torch.empty((total,), dtype=torch.int32, device=f0.device)
+        score = torch.empty((len(nf),), dtype=torch.float64, device=f0.device)
+        cl = torch.empty((total, K), dtype=torch.int32, device=f0.device) if want_cand else None
+        cc = ctx.empty((total, K)) if want_cand else None
+        return f0, lag, score, cl, cc
+
+    def _run_track(self, wavs, want_cand=False):
+        """-> per utterance lists (f0, lag, candidate lags, candidate costs) and the (B,) float64 scores: one engine call."""
+        ctx = Context.get(self._device)
+        xs, lens, x = _pack(ctx, list(wavs), "Pitch")
+        nf = [self.frames(n) for n in lens]
+        if max(nf) > PITCH_MAX_TRACK_FRAMES:
+            raise NotImplementedError(f"pitch: a track of {max(nf)} frames; the tracker's limit is {PITCH_MAX_TRACK_FRAMES}")
+        f0, lag, score, cl, cc = self._track_outputs(ctx, nf, want_cand)
+        cfg = self._track_cfg()
+        _capi.check(ctx.lib.pk_pitch_track_run(self.h, dptr(x), _i32p(lens), len(xs), C.byref(cfg), dptr(f0), _vptr(lag),
+                                               _vptr(score), _vptr(cl), _vptr(cc), 0))
+        split = lambda t: None if t is None else list(torch.split(t, nf))   # noqa: E731
+        return split(f0), split(lag), split(cl), split(cc), score
+
+    def candidates(self, wavs):
+        """Ragged list -> per utterance ``(lags, costs)``: (frames, max_candidates) int32 and float32, a frame's candidates by
+        ascending lag, empty slots with lag 0 and cost +inf."""
+        _, _, cl, cc, _ = self._run_track(wavs, want_cand=True)
+        return [(a, wrap(b)) for a, b in zip(cl, cc)]
+
+    def track_viterbi(self, wavs, return_score=False):
+        """Ragged list -> per utterance ``(f0_raw, lag)`` of the Viterbi path over the frames' candidates, whatever the
+        handle's ``tracker`` is; with ``return_score`` ``(f0_raw, lag, score)``, the path's cost as a float."""
+        f0, lag, _, _, score = self._run_track(wavs)
+        if not return_score:
+            return [(wrap(a), b) for a, b in zip(f0, lag)]
+        return [(wrap(a), b, float(c)) for a, b, c in zip(f0, lag, score.cpu())]
+
+    def track_from_cmnd(self, rows):
+        """A list of (frames, tau_max + 1) d' arrays (``cmnd``'s layout) -> per track a dict of ``f0``, ``lag``, ``score``
+        (float), ``cand_lag`` and ``cand_cost``: the tracker on rows of the caller."""
+        ctx = Context.get(self._device)
+        rs = [ctx.to_device(r) for r in rows]
+        if not rs:
+            return []
+        for r in rs:
+            if r.dim() != 2 or r.shape[1] != self.tau_max + 1:
+                raise ValueError(f"pitch: d' rows of shape {tuple(r.shape)}; (frames, tau_max + 1 = {self.tau_max + 1}) is needed")
+        nf = [int(r.shape[0]) for r in rs]
+        if min(nf) < 1:
+            raise ValueError("pitch: an empty track")
+        if max(nf) > PITCH_MAX_TRACK_FRAMES:
+            raise NotImplementedError(f"pitch: a track of {max(nf)} frames; the tracker's limit is {PITCH_MAX_TRACK_FRAMES}")
+        x = rs[0].contiguous() if len(rs) == 1 else torch.cat(rs)
+        f0, lag, score, cl, cc = self._track_outputs(ctx, nf, True)
+        cfg = self._track_cfg()
+        _capi.check(ctx.lib.pk_pitch_track_from_cmnd(self.h, dptr(x), _i32p(np.array(nf, dtype=np.int32)), len(rs), C.byref(cfg),
+                                                     dptr(f0), _vptr(lag), _vptr(score), _vptr(cl), _vptr(cc), 0))
+        sc = score.cpu()
+        return [dict(f0=wrap(a), lag=b, score=float(c), cand_lag=d, cand_cost=wrap(e))
+                for a, b, c, d, e in zip(torch.split(f0, nf), torch.split(lag, nf), sc, torch.split(cl, nf), torch.split(cc, nf))]
 
     def cmnd(self, wav):
         """(frames, tau_max + 1): the cumulative-mean-normalised difference d'(0 ... tau_max) of every frame."""
@@ -491,10 +591,15 @@ class Pitch:
             f0 = self._average_by_duration(f0, duration)
         return f0
 
-    def get_pitch_batch(self, wavs, durations=None, use_continuous_f0=True, use_log_f0=True, use_token_averaged_f0=True):
-        """``get_pitch`` for a ragged list: one engine call for the estimator and one for the continuous / log step."""
+    def get_pitch_batch(self, wavs, durations=None, use_continuous_f0=True, use_log_f0=True, use_token_averaged_f0=True,
+                        tracker=None):
+        """``get_pitch`` for a ragged list: one engine call for the estimator and one for the continuous / log step.
+        ``tracker`` overrides the handle's for this call."""
         wavs = list(wavs)
-        f0 = self._run(wavs)[0]
+        tracker = self.tracker if tracker is None else tracker
+        if tracker not in PITCH_TRACKERS:
+            raise ValueError(f"pitch: tracker = {tracker!r}; one of {PITCH_TRACKERS}")
+        f0 = self._run_track(wavs)[0] if tracker == "viterbi" else self._run(wavs)[0]
         if use_continuous_f0 or use_log_f0:
             f0 = continuous_f0_batch(f0, use_log_f0, self._device, fill=use_continuous_f0)
         f0 = [wrap(f) for f in f0]

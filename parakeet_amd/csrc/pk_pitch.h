@@ -18,6 +18,12 @@ constexpr int PT_MAX_HOP = 16384;
 constexpr int PT_MAX_F = 32;             // frames per tile
 constexpr int PT_MAX_LDS = 16128;        // floats of LDS per workgroup: the staged span and the F rows of d (63 KiB)
 constexpr int PT_SCAN_CHUNK = 256;       // frames per scan step of the continuous-f0 kernel
+// the tracker (k_pitch_cand, k_pitch_viterbi)
+constexpr int PTK_MAX_K = 8;             // candidates per frame: the 64 lanes of a wave are the 8 x 8 (predecessor, state) pairs
+constexpr int PTK_SLOTS = (PT_MAX_TAU + 63) / 64;   // lags per lane of the candidate kernel
+constexpr int PTK_CH = 64;               // frames whose candidates are staged in LDS at a time
+constexpr int PTK_BP_LDS = 4096;         // frames whose backpointer words (8 bytes each) stay in LDS; longer tracks use a workspace
+constexpr int PTK_MAX_FRAMES = 1 << 22;  // frames per track
 
 struct pt_plan {
     int L = 0;                           // W + tau_max
