@@ -1096,6 +1096,55 @@ int pk_mas_lds_words(int32_t* words);
 int pk_focus_rate_run(pk_ctx* ctx, const float* att, const int64_t* offs, int64_t map_stride, int64_t row_stride,
                       const int32_t* maps, const int32_t* rows, const int32_t* cols, int32_t B, double* rates_out);
 
+/* ------------------------------------- dynamic time warping and its path statistics */
+/* Unconstrained dynamic time warping of ragged batches and float64 sums along the path (csrc/dtw.hip): what
+ * mel-cepstral distortion and log-F0 RMSE of free-running synthesis are taken along (parakeet_amd/metrics.py).  The
+ * definition is this project's own (csrc/pk_dtw.h states it in full: squared Euclidean local cost, no band, no slope weights).
+ * Data pointers are DEVICE pointers; offs_*, rows, cols are HOST arrays; offsets and strides count floats.  A pair's results
+ * are the same bits alone, in any batch and at any position in it; its neighbours in a packed buffer and the padding of a
+ * padded tensor are never read.
+ *
+ * pk_dtw_run: pair b has rows[b] = N rows (frames of x) and cols[b] = M columns (frames of y).
+ *   mode 0: x_or_cost holds the float32 cost matrices, row i of pair b at x_or_cost + offs_x[b] + i * stride_x (stride 0:
+ *           cols[b]; offs_x NULL: the matrices follow one another); y, offs_y, stride_y, D, k0, k1 are not looked at.
+ *   mode 1: x_or_cost holds the (N, D) features x, y the (M, D) features y (row strides 0: D; NULL offsets: the pairs follow
+ *           one another); c(i, j) = (float) sum_{k0 <= k < k1} ((double)x[i, k] - (double)y[j, k])^2, summed ascending with
+ *           separate float64 operations, formed on the device into a workspace of the context (pk_dtw_cost_cap).
+ *   Q(0, 0) = c(0, 0), Q(i, j) = c(i, j) + min(Q(i - 1, j - 1), Q(i - 1, j), Q(i, j - 1)) in float64; the predecessor is the
+ *   smallest, ties to the diagonal, then to (i - 1, j).
+ *   ix_out, iy_out  packed int32, N + M - 1 entries per pair (pair b starts at the sum of those before it): the path in
+ *                   forward order from (0, 0) to (N - 1, M - 1); entries from the path's length on are never written;
+ *   len_out         (B) int32: the path's length P, max(N, M) <= P <= N + M - 1;
+ *   cost_out        NULL, or (B) double: Q(N - 1, M - 1);
+ *   status_out      NULL, or (B) int32: 1 if a c(i, j) is not finite (that pair's path is then unspecified), else 0.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit; nothing is launched): rows, cols <= 4096, D <= 128,
+ * B <= 65535.  PK_EINVAL: a NULL pointer that is needed, B <= 0, an empty pair, a column range outside [0, D), a stride
+ * below the extent it spans or without offsets, a negative offset, an unknown mode. */
+int pk_dtw_run(pk_ctx* ctx, int32_t mode, const float* x_or_cost, const float* y, const int64_t* offs_x, const int64_t* offs_y,
+               int64_t stride_x, int64_t stride_y, int32_t D, int32_t k0, int32_t k1, const int32_t* rows, const int32_t* cols,
+               int32_t B, int32_t* ix_out, int32_t* iy_out, int32_t* len_out, double* cost_out, int32_t* status_out);
+/* Feature mode's cost matrices alone (the kernel pk_dtw_run launches): cost_out packed float, sum rows * cols, contiguous. */
+int pk_dtw_cost(pk_ctx* ctx, const float* x, const float* y, const int64_t* offs_x, const int64_t* offs_y, int64_t stride_x,
+                int64_t stride_y, int32_t D, int32_t k0, int32_t k1, const int32_t* rows, const int32_t* cols, int32_t B,
+                float* cost_out);
+/* The 32-bit decision words of a pair that stay in LDS; a pair has cols * ceil(rows / R) of them, R = the smallest of 1, 2,
+ * 4, 8, 16 with 64 R >= rows (16 beyond), and keeps them in a global workspace when that is more. */
+int pk_dtw_lds_words(int32_t* words);
+/* The cap in bytes on feature mode's cost workspace (256 MiB unless set; process-wide): set_bytes 0 leaves it, bytes_out may
+ * be NULL.  A call whose matrices exceed it runs in several launches over consecutive pairs; a launch holds at least one
+ * pair, whatever the cap. */
+int pk_dtw_cost_cap(int64_t set_bytes, int64_t* bytes_out);
+/* Sums along paths.  ix, iy, len: as pk_dtw_run writes them for the same rows, cols (DEVICE pointers).  x, y and the column
+ * range as in mode 1.  mask_x, mask_y: NULL, or packed uint8 (sum rows / sum cols).  s_p is the float64 sum of step p.
+ *   sums_out    (B, 2) double: sum s_p, sum sqrt(s_p) over the steps whose two masks are set (all steps without masks), in
+ *               the fixed order csrc/pk_dtw.h states; no atomics;
+ *   counts_out  (B, 4) int64: the steps with (mask_x, mask_y) set = (1, 1), (1, 0), (0, 1), (0, 0);
+ *   status_out  NULL, or (B) int32: 2 if len or a path entry lies outside the pair (such steps are left out), else 0. */
+int pk_dtw_path_stats(pk_ctx* ctx, const int32_t* ix, const int32_t* iy, const int32_t* len, const float* x, const float* y,
+                      const int64_t* offs_x, const int64_t* offs_y, int64_t stride_x, int64_t stride_y, int32_t D, int32_t k0,
+                      int32_t k1, const int32_t* rows, const int32_t* cols, int32_t B, const uint8_t* mask_x,
+                      const uint8_t* mask_y, double* sums_out, int64_t* counts_out, int32_t* status_out);
+
 /* ------------------------------------------------------- feature statistics */
 /* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
  * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature

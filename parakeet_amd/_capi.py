@@ -324,6 +324,13 @@ def _declare(lib):
                                  C.c_void_p, f32p]),
         "pk_mas_lds_words": (C.c_int, [i32p]),
         "pk_focus_rate_run": (C.c_int, [vp, f32p, i64p, i64, i64, i32p, i32p, i32p, i32, C.c_void_p]),
+        "pk_dtw_run": (C.c_int, [vp, i32, f32p, f32p, i64p, i64p, i64, i64, i32, i32, i32, i32p, i32p, i32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pk_dtw_cost": (C.c_int, [vp, f32p, f32p, i64p, i64p, i64, i64, i32, i32, i32, i32p, i32p, i32, f32p]),
+        "pk_dtw_lds_words": (C.c_int, [i32p]),
+        "pk_dtw_cost_cap": (C.c_int, [i64, i64p]),
+        "pk_dtw_path_stats": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, i64p, i64p, i64, i64, i32, i32, i32,
+                                        i32p, i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "pk_stats_destroy": (None, [vp]),
         "pk_stats_reset": (C.c_int, [vp, f32p]),

@@ -6,7 +6,12 @@ FastSpeech recipe needs, ``focus_rate`` / ``select_map`` FastSpeech's criterion 
 ``utt|speaker|ph d ph d ...`` file examples/fastspeech2_features.py reads.  The definition is this project's own
 (csrc/pk_align.h); these are a teacher's attention boundaries, NOT the Montreal Forced Aligner's forced alignment.  Maps that
 are device tensors stay on the device: views of one packed tensor (what ``teacher_forced_batch`` returns) are addressed
-in place.  Rows are decoder steps S, columns tokens T."""
+in place.  Rows are decoder steps S, columns tokens T.
+
+``dtw`` / ``dtw_features`` / ``path_stats`` (csrc/pk_dtw.h) are unconstrained dynamic time warping of two
+sequences of different lengths and float64 sums along its path: what ``parakeet_amd.metrics`` takes mel-cepstral distortion
+and log-F0 RMSE along.  That definition is this project's own too (squared Euclidean local cost, no band, no slope weights)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -16,7 +21,7 @@ from . import _capi
 from .runtime import Context, dptr, wrap
 
 __all__ = ["monotonic_align", "durations_from_attention", "focus_rate", "select_map", "write_durations", "MAX_TOKENS",
-           "MAX_ROWS"]
+           "MAX_ROWS", "dtw", "dtw_features", "path_stats", "DTWPath", "PathStats", "DTW_MAX_FRAMES", "DTW_MAX_DIM"]
 
 MAX_TOKENS, MAX_ROWS = 1024, 16384        # csrc/pk_align.h: MAS_MAX_COLS, MAS_MAX_ROWS
 
@@ -250,3 +255,205 @@ def write_durations(path, utt_ids, speakers, phones, durations):
         lines.append(f"{u}|{spk}|" + " ".join(f"{p} {v}" for p, v in zip(ph, d)))
     with open(path, "wt", encoding="utf-8") as f:
         f.write("".join(line + "\n" for line in lines))
+
+
+# --------------------------------------------------------------------------------------------- dynamic time warping (4.7b)
+DTW_MAX_FRAMES, DTW_MAX_DIM = 4096, 128    # csrc/pk_dtw.h: DTW_MAX_ROWS / DTW_MAX_COLS, DTW_MAX_DIM
+
+PathStats = collections.namedtuple("PathStats", "sum_sq sum_sqrt n11 n10 n01 n00 length")
+
+
+class DTWPath:
+    """One pair's warping path: ``ix``, ``iy`` int32 device tensors of ``length`` entries (forward, from (0, 0) to
+    (rows - 1, cols - 1)), ``cost`` = Q(rows - 1, cols - 1) as a float."""
+    __slots__ = ("ix", "iy", "cost", "length", "rows", "cols", "_batch", "_index")
+
+    def __init__(self, ix, iy, cost, length, rows, cols, batch=None, index=0):
+        self.ix, self.iy, self.cost, self.length, self.rows, self.cols = ix, iy, float(cost), int(length), int(rows), int(cols)
+        self._batch, self._index = batch, index
+
+    def __repr__(self):
+        return f"DTWPath({self.rows} x {self.cols}, length={self.length}, cost={self.cost!r})"
+
+
+def _dtw_envelope(r, c):
+    for b in range(r.size):
+        if r[b] > DTW_MAX_FRAMES:
+            raise NotImplementedError(f"pair {b} has {int(r[b])} rows; the engine's envelope is 1 ... {DTW_MAX_FRAMES}")
+        if c[b] > DTW_MAX_FRAMES:
+            raise NotImplementedError(f"pair {b} has {int(c[b])} columns; the engine's envelope is 1 ... {DTW_MAX_FRAMES}")
+
+
+def _features(x, lens, what):
+    """One (n, D) sequence, a list of such, or a padded (B, nmax, D) tensor with ``lens`` -> (seqs, n (B,), D, single, padded)."""
+    if lens is not None:
+        if not _is_map(x) or len(x.shape) != 3:
+            raise ValueError(f"{what}: lengths describe one padded tensor of shape (B, nmax, D), got "
+                             + (f"shape {tuple(x.shape)}" if _is_map(x) else type(x).__name__))
+        B = int(x.shape[0])
+        if B == 0:
+            raise ValueError(f"{what}: no sequences given")
+        n = _lengths(lens, B, f"{what} lengths")
+        if (n < 1).any() or (n > x.shape[1]).any():
+            raise ValueError(f"{what}: lengths {n.tolist()} do not lie in 1 ... {int(x.shape[1])}")
+        return x, n, int(x.shape[2]), False, True
+    single = _is_map(x)
+    seqs = [x] if single else list(x)
+    if not seqs:
+        raise ValueError(f"{what}: no sequences given")
+    for b, m in enumerate(seqs):
+        if not _is_map(m) or len(m.shape) != 2:
+            raise ValueError(f"{what} {b}: expected features of shape (frames, D)"
+                             + (f", got shape {tuple(m.shape)}" if _is_map(m) else f", got {type(m).__name__}"))
+        if min(m.shape) < 1:
+            raise ValueError(f"{what} {b} is empty: shape {tuple(m.shape)}")
+        if m.shape[1] != seqs[0].shape[1]:
+            raise ValueError(f"{what} {b} has {int(m.shape[1])} feature columns, {what} 0 has {int(seqs[0].shape[1])}")
+    return seqs, np.array([m.shape[0] for m in seqs], dtype=np.int64), int(seqs[0].shape[1]), single, False
+
+
+def _columns(columns, D):
+    if D > DTW_MAX_DIM:
+        raise NotImplementedError(f"feature dimension {D}; the engine's envelope is 1 ... {DTW_MAX_DIM}")
+    k0, k1 = (0, D) if columns is None else (int(columns[0]), int(columns[1]))
+    if not 0 <= k0 < k1 <= D:
+        raise ValueError(f"columns [{k0}, {k1}) do not lie in [0, {D})")
+    return k0, k1
+
+
+def _pair_features(x, y, x_lens, y_lens, columns):
+    xs, n, D, single, xpad = _features(x, x_lens, "x")
+    ys, m, Dy, ysingle, ypad = _features(y, y_lens, "y")
+    if n.size != m.size or single != ysingle:
+        raise ValueError(f"{n.size} sequences x, {m.size} sequences y")
+    if D != Dy:
+        raise ValueError(f"x has {D} feature columns, y has {Dy}")
+    k0, k1 = _columns(columns, D)
+    _dtw_envelope(n, m)
+    ctx = Context.get()
+    dd = np.full(n.size, D, dtype=np.int64)
+    kx, px, ox, _, sx = _place(ctx, xs, n, dd, 1, xpad)
+    ky, py, oy, _, sy = _place(ctx, ys, m, dd, 1, ypad)
+    return ctx, (kx, ky), px, py, ox, oy, int(sx), int(sy), D, k0, k1, n, m, single
+
+
+def _dtw_call(ctx, mode, px, py, ox, oy, sx, sy, D, k0, k1, r, c, single, keep):
+    B = int(r.size)
+    r32, c32 = _i32(r), _i32(c)
+    cap = (r + c - 1).astype(np.int64)
+    po = np.concatenate(([0], np.cumsum(cap)))
+    ix = ctx.empty((int(po[-1]),), dtype=torch.int32)
+    iy = ctx.empty((int(po[-1]),), dtype=torch.int32)
+    ln = ctx.empty((B,), dtype=torch.int32)
+    cost = ctx.empty((B,), dtype=torch.float64)
+    status = ctx.empty((B,), dtype=torch.int32)
+    _capi.check(ctx.lib.pk_dtw_run(ctx.handle, int(mode), px, py, _p(ox, C.c_int64), None if oy is None else _p(oy, C.c_int64),
+                                   int(sx), int(sy), int(D), int(k0), int(k1), _p(r32, C.c_int32), _p(c32, C.c_int32), B,
+                                   dptr(ix), dptr(iy), dptr(ln), dptr(cost), dptr(status)))
+    st, P, q = status.cpu().numpy(), ln.cpu().numpy(), cost.cpu().numpy()
+    del keep
+    if st.any():
+        raise FloatingPointError(f"dynamic time warping: pair(s) {[int(b) for b in np.flatnonzero(st)]} hold a local cost that "
+                                 "is not finite")
+    batch = (ix, iy, ln, r32, c32)
+    out = [DTWPath(wrap(ix[po[b]:po[b] + P[b]]), wrap(iy[po[b]:po[b] + P[b]]), q[b], P[b], r[b], c[b], batch, b)
+           for b in range(B)]
+    return out[0] if single else out
+
+
+def dtw(cost, rows=None, cols=None):
+    """Dynamic time warping through given local costs (``pk_dtw_run``, matrix mode).  ``cost``: one (N, M) matrix, a list of
+    (N_b, M_b) matrices, or a padded (B, Nmax, Mmax) tensor with ``rows`` / ``cols`` (B,), the valid lengths; float32, numpy
+    or tensors on any device (device tensors stay there; views of one packed tensor are addressed in place).  Returns a
+    ``DTWPath`` (``ix``, ``iy``, ``cost``, ``length``) per pair: a list for a list or a padded tensor, the bare item for one
+    matrix.  NotImplementedError outside 1 <= N, M <= 4096; FloatingPointError naming the pairs with a cost that is not
+    finite."""
+    maps, r, c, _, _, single, padded = _layout(cost, rows, cols, 0)
+    _dtw_envelope(r, c)
+    ctx = Context.get()
+    keep, ptr, offs, _, row_stride = _place(ctx, maps, r, c, 1, padded)
+    return _dtw_call(ctx, 0, ptr, None, offs, None, row_stride, 0, 0, 0, 0, r, c, single, keep)
+
+
+def dtw_features(x, y, columns=None, *, x_lens=None, y_lens=None):
+    """Dynamic time warping of feature sequences (``pk_dtw_run``, feature mode): the local cost is the squared Euclidean
+    distance over the feature columns ``columns = (k0, k1)`` (all by default), formed on the device in float64 and rounded to
+    float32 once.  ``x`` / ``y``: one (N, D) / (M, D) sequence each, two lists of such, or padded (B, Nmax, D) / (B, Mmax, D)
+    tensors with ``x_lens`` / ``y_lens``.  Returns as ``dtw``.  NotImplementedError outside 1 <= N, M <= 4096, D <= 128."""
+    ctx, keep, px, py, ox, oy, sx, sy, D, k0, k1, n, m, single = _pair_features(x, y, x_lens, y_lens, columns)
+    return _dtw_call(ctx, 1, px, py, ox, oy, sx, sy, D, k0, k1, n, m, single, keep)
+
+
+def _pack_paths(ctx, paths, n, m):
+    """-> (ix, iy, len) device buffers in pk_dtw_run's layout for pairs of n x m frames.  The buffers of one ``dtw`` call are
+    used as they are."""
+    B = n.size
+    if len(paths) != B:
+        raise ValueError(f"{len(paths)} paths, {B} pairs of sequences")
+    for b, p in enumerate(paths):
+        if isinstance(p, DTWPath) and (p.rows, p.cols) != (int(n[b]), int(m[b])):
+            raise ValueError(f"path {b} is one of a {p.rows} x {p.cols} pair, the sequences have {int(n[b])} x {int(m[b])} frames")
+    b0 = paths[0]._batch if isinstance(paths[0], DTWPath) else None
+    if b0 is not None and b0[2].numel() == B and b0[0].device == ctx.device \
+            and all(isinstance(p, DTWPath) and p._batch is b0 and p._index == b for b, p in enumerate(paths)):
+        return b0[0], b0[1], b0[2]
+    cap = (n + m - 1).astype(np.int64)
+    po = np.concatenate(([0], np.cumsum(cap)))
+    ix = torch.zeros((int(po[-1]),), dtype=torch.int32, device=ctx.device)
+    iy = torch.zeros((int(po[-1]),), dtype=torch.int32, device=ctx.device)
+    ln = np.zeros(B, dtype=np.int32)
+    for b, p in enumerate(paths):
+        a, c = (p.ix, p.iy) if isinstance(p, DTWPath) else p
+        a, c = ctx.to_device(a, dtype=torch.int32).reshape(-1), ctx.to_device(c, dtype=torch.int32).reshape(-1)
+        if a.numel() != c.numel() or not 1 <= a.numel() <= cap[b]:
+            raise ValueError(f"path {b}: {a.numel()} and {c.numel()} entries for a pair of {int(n[b])} x {int(m[b])} frames")
+        ix[po[b]:po[b] + a.numel()] = a
+        iy[po[b]:po[b] + a.numel()] = c
+        ln[b] = a.numel()
+    return ix, iy, ctx.to_device(ln, dtype=torch.int32)
+
+
+def _pack_masks(ctx, masks, lens, single, what):
+    """Per-pair masks (or one padded (B, nmax) mask) -> one packed uint8 device tensor, sum of ``lens`` entries."""
+    if masks is None:
+        return None
+    padded = not single and _is_map(masks)
+    ms = [masks] if single else list(masks)
+    if len(ms) != lens.size:
+        raise ValueError(f"{len(ms)} {what} masks, {lens.size} pairs")
+    out = []
+    for b, mk in enumerate(ms):
+        t = (mk.as_subclass(torch.Tensor) if isinstance(mk, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mk))).reshape(-1)
+        if t.numel() < lens[b] or (not padded and t.numel() != lens[b]):
+            raise ValueError(f"{what} mask {b} has {t.numel()} entries, the sequence {int(lens[b])} frames")
+        out.append((t[:int(lens[b])] != 0).to(device=ctx.device, dtype=torch.uint8))
+    return torch.cat(out).contiguous()
+
+
+def path_stats(paths, x, y, columns=None, mask_x=None, mask_y=None, *, x_lens=None, y_lens=None):
+    """Float64 sums along warping paths (``pk_dtw_path_stats``).  ``paths``: what ``dtw`` / ``dtw_features`` returned for
+    these pairs (or ``(ix, iy)`` arrays); ``x`` / ``y`` and ``columns`` as for ``dtw_features``; ``mask_x`` / ``mask_y``: per
+    pair a (N,) / (M,) mask (non-zero: set), or padded (B, Nmax) / (B, Mmax) masks.  With s_p the float64 squared distance of
+    step p over the columns, returns per pair ``PathStats``: ``sum_sq`` = sum s_p and ``sum_sqrt`` = sum sqrt(s_p) over the
+    steps whose two masks are set (all steps without masks), the counts ``n11, n10, n01, n00`` of the steps by (mask_x,
+    mask_y), and the path's ``length``.  The sums are taken in a fixed order (csrc/pk_dtw.h): the same bits in any batch."""
+    ctx, keep, px, py, ox, oy, sx, sy, D, k0, k1, n, m, single = _pair_features(x, y, x_lens, y_lens, columns)
+    plist = [paths] if isinstance(paths, DTWPath) or (single and isinstance(paths, tuple)) else list(paths)
+    ix, iy, ln = _pack_paths(ctx, plist, n, m)
+    mx, my = _pack_masks(ctx, mask_x, n, single, "x"), _pack_masks(ctx, mask_y, m, single, "y")
+    B = int(n.size)
+    r32, c32 = _i32(n), _i32(m)
+    sums = ctx.empty((B, 2), dtype=torch.float64)
+    counts = ctx.empty((B, 4), dtype=torch.int64)
+    status = ctx.empty((B,), dtype=torch.int32)
+    _capi.check(ctx.lib.pk_dtw_path_stats(ctx.handle, dptr(ix), dptr(iy), dptr(ln), px, py, _p(ox, C.c_int64), _p(oy, C.c_int64),
+                                          sx, sy, D, k0, k1, _p(r32, C.c_int32), _p(c32, C.c_int32), B,
+                                          None if mx is None else dptr(mx), None if my is None else dptr(my), dptr(sums),
+                                          dptr(counts), dptr(status)))
+    st, s, cn, P = status.cpu().numpy(), sums.cpu().numpy(), counts.cpu().numpy(), ln.cpu().numpy()
+    del keep
+    if st.any():
+        raise ValueError(f"path statistics: the path(s) of pair(s) {[int(b) for b in np.flatnonzero(st)]} leave their pair")
+    out = [PathStats(float(s[b, 0]), float(s[b, 1]), int(cn[b, 0]), int(cn[b, 1]), int(cn[b, 2]), int(cn[b, 3]), int(P[b]))
+           for b in range(B)]
+    return out[0] if single else out

@@ -150,6 +150,11 @@ struct pk_ctx_scratch {
     pk_dbuf seq_io;
     pk_dbuf mas_tab;     // align.hip: the call's table of pk_mas_run / pk_focus_rate_run, the decision words that do not fit LDS
     pk_dbuf mas_bits;
+    pk_dbuf dtw_tab;     // dtw.hip: the call's tables, feature mode's cost matrices (capped: pk_dtw.h), the decision words that do
+    pk_dbuf dtw_cost;    // not fit LDS, the carry rows of pairs of several passes, the reversed paths
+    pk_dbuf dtw_bits;
+    pk_dbuf dtw_carry;
+    pk_dbuf dtw_rev;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

@@ -90,6 +90,11 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->seq_io.release();
         kv.second->mas_tab.release();
         kv.second->mas_bits.release();
+        kv.second->dtw_tab.release();
+        kv.second->dtw_cost.release();
+        kv.second->dtw_bits.release();
+        kv.second->dtw_carry.release();
+        kv.second->dtw_rev.release();
         delete kv.second;
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
