@@ -1145,6 +1145,34 @@ int pk_dtw_path_stats(pk_ctx* ctx, const int32_t* ix, const int32_t* iy, const i
                       int32_t k1, const int32_t* rows, const int32_t* cols, int32_t B, const uint8_t* mask_x,
                       const uint8_t* mask_y, double* sums_out, int64_t* counts_out, int32_t* status_out);
 
+/* ------------------------------------------------- edit distance and its alignment */
+/* The edit (Levenshtein) distance of ragged batches of token sequences and the alignment it comes from (csrc/edit.hip,
+ * DESIGN 4.7c): what word, character and phone error rates are counted from (parakeet_amd/utils/error_rate.py).  csrc/pk_edit.h
+ * states the definition in full.  ref, hyp and the outputs are DEVICE pointers; offs_*, n, m are HOST arrays; offsets count
+ * ids.  A pair's results are the same bits alone, in any batch and at any position in it; its neighbours in a packed buffer
+ * and the padding of a padded tensor are never read.
+ *
+ * pk_edit_run: pair b has n[b] = N >= 0 int32 ids at ref + offs_ref[b] and m[b] = M >= 0 at hyp + offs_hyp[b] (NULL offsets: the
+ * pairs follow one another).  Any int32 value is an id; only equality is used.
+ *   D(i, 0) = i, D(0, j) = j, D(i, j) = D(i - 1, j - 1) if ref[i - 1] == hyp[j - 1], else 1 + min(D(i - 1, j - 1), D(i - 1, j),
+ *   D(i, j - 1)); the walk back from (N, M) takes a hit on equal ids, else the first of substitution (i - 1, j - 1), deletion
+ *   (i - 1, j), insertion (i, j - 1) whose value is D(i, j) - 1; insertions in row 0, deletions in column 0.
+ *   mode 0: dist_out alone is written (counts_out, ops_out, len_out are not looked at): no ops are kept, nothing is walked.
+ *   mode 1: all four.
+ *   dist_out    (B) int32: D(N, M);
+ *   counts_out  (B, 4) int32: hits, substitutions, deletions, insertions;
+ *   ops_out     packed uint8, N + M entries per pair (pair b starts at the sum of those before it): the ops in forward order,
+ *               0 hit, 1 substitution, 2 deletion, 3 insertion; entries from len_out[b] on are never written;
+ *   len_out     (B) int32: their number P, max(N, M) <= P <= N + M.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit; nothing is launched): n, m <= 4096, B <= 65535.  PK_EINVAL: a
+ * NULL pointer that is needed, B <= 0, a negative length or offset, an unknown mode. */
+int pk_edit_run(pk_ctx* ctx, const int32_t* ref, const int32_t* hyp, const int64_t* offs_ref, const int64_t* offs_hyp,
+                const int32_t* n, const int32_t* m, int32_t B, int32_t mode, int32_t* dist_out, int32_t* counts_out,
+                uint8_t* ops_out, int32_t* len_out);
+/* The 32-bit op words of a pair that stay in LDS (mode 1); a pair has m * ceil(n / R) of them, R = the smallest of 1, 2, 4,
+ * 8, 16 with 64 R >= n (16 beyond), and keeps them in a global workspace when that is more. */
+int pk_edit_lds_words(int32_t* words);
+
 /* ------------------------------------------------------- feature statistics */
 /* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
  * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature

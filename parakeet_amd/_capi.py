@@ -331,6 +331,9 @@ def _declare(lib):
         "pk_dtw_cost_cap": (C.c_int, [i64, i64p]),
         "pk_dtw_path_stats": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, i64p, i64p, i64, i64, i32, i32, i32,
                                         i32p, i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pk_edit_run": (C.c_int, [vp, C.c_void_p, C.c_void_p, i64p, i64p, i32p, i32p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+        "pk_edit_lds_words": (C.c_int, [i32p]),
         "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "pk_stats_destroy": (None, [vp]),
         "pk_stats_reset": (C.c_int, [vp, f32p]),

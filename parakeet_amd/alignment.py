@@ -10,7 +10,11 @@ in place.  Rows are decoder steps S, columns tokens T.
 
 ``dtw`` / ``dtw_features`` / ``path_stats`` (csrc/pk_dtw.h) are unconstrained dynamic time warping of two
 sequences of different lengths and float64 sums along its path: what ``parakeet_amd.metrics`` takes mel-cepstral distortion
-and log-F0 RMSE along.  That definition is this project's own too (squared Euclidean local cost, no band, no slope weights)."""
+and log-F0 RMSE along.  That definition is this project's own too (squared Euclidean local cost, no band, no slope weights).
+
+``edit_distance`` / ``edit_align`` / ``confusions`` (csrc/pk_edit.h) are the Levenshtein distance of token-id
+sequences -- the recurrence of parakeet/utils/error_rate.py -- and the alignment it comes from (hits, substitutions, deletions,
+insertions; this project's own tie rule): what ``parakeet_amd.utils.error_rate`` counts word and character errors with."""
 import collections
 import ctypes as C
 
@@ -21,7 +25,9 @@ from . import _capi
 from .runtime import Context, dptr, wrap
 
 __all__ = ["monotonic_align", "durations_from_attention", "focus_rate", "select_map", "write_durations", "MAX_TOKENS",
-           "MAX_ROWS", "dtw", "dtw_features", "path_stats", "DTWPath", "PathStats", "DTW_MAX_FRAMES", "DTW_MAX_DIM"]
+           "MAX_ROWS", "dtw", "dtw_features", "path_stats", "DTWPath", "PathStats", "DTW_MAX_FRAMES", "DTW_MAX_DIM",
+           "edit_distance", "edit_align", "confusions", "EditAlignment", "EditCounts", "Confusions", "EDIT_MAX_TOKENS",
+           "EDIT_MAX_BATCH"]
 
 MAX_TOKENS, MAX_ROWS = 1024, 16384        # csrc/pk_align.h: MAS_MAX_COLS, MAS_MAX_ROWS
 
@@ -457,3 +463,148 @@ def path_stats(paths, x, y, columns=None, mask_x=None, mask_y=None, *, x_lens=No
     out = [PathStats(float(s[b, 0]), float(s[b, 1]), int(cn[b, 0]), int(cn[b, 1]), int(cn[b, 2]), int(cn[b, 3]), int(P[b]))
            for b in range(B)]
     return out[0] if single else out
+
+
+# ------------------------------------------------------------------------------------- edit distance and its alignment (4.7c)
+EDIT_MAX_TOKENS, EDIT_MAX_BATCH = 4096, 65535    # csrc/pk_edit.h: EDIT_MAX_LEN; pairs in one call of pk_edit_run
+HIT, SUBSTITUTION, DELETION, INSERTION = 0, 1, 2, 3
+
+EditCounts = collections.namedtuple("EditCounts", "hits substitutions deletions insertions")
+Confusions = collections.namedtuple("Confusions", "substitutions deletions insertions")
+
+
+class EditAlignment:
+    """One pair's alignment: ``ops`` a uint8 device tensor of ``length`` entries in forward order (0 hit, 1 substitution,
+    2 deletion, 3 insertion), ``distance`` = substitutions + deletions + insertions, ``counts`` an ``EditCounts``,
+    ``ref_len`` / ``hyp_len`` the pair's lengths."""
+    __slots__ = ("ops", "distance", "counts", "length", "ref_len", "hyp_len")
+
+    def __init__(self, ops, distance, counts, length, ref_len, hyp_len):
+        self.ops, self.distance, self.counts = ops, int(distance), EditCounts(*(int(c) for c in counts))
+        self.length, self.ref_len, self.hyp_len = int(length), int(ref_len), int(hyp_len)
+
+    def index_pairs(self):
+        """``(ref_index, hyp_index)``: int64 numpy arrays of ``length`` entries, the ids a step pairs; -1 at a gap (the ref
+        index of an insertion, the hyp index of a deletion)."""
+        ops = self.ops.as_subclass(torch.Tensor).cpu().numpy()
+        ri, hi = np.cumsum(ops != INSERTION) - 1, np.cumsum(ops != DELETION) - 1
+        return np.where(ops != INSERTION, ri, -1).astype(np.int64), np.where(ops != DELETION, hi, -1).astype(np.int64)
+
+    def __repr__(self):
+        return f"EditAlignment({self.ref_len} x {self.hyp_len}, distance={self.distance}, {self.counts})"
+
+
+def _is_scalar(v):
+    return isinstance(v, (int, float, np.number)) or (isinstance(v, (np.ndarray, torch.Tensor)) and v.ndim == 0)
+
+
+def _id_seqs(ctx, x, lens, what):
+    """One id sequence, a list of them, or a padded (B, Lmax) tensor with ``lens`` -> (keep, pointer, offs (B,) int64,
+    n (B,) int64, single).  An int32 device tensor is addressed in place; anything else is packed by one upload."""
+    if lens is not None:
+        if not _is_map(x) or len(x.shape) != 2:
+            raise ValueError(f"{what}: lengths describe one padded tensor of shape (B, Lmax), got "
+                             + (f"shape {tuple(x.shape)}" if _is_map(x) else type(x).__name__))
+        B, L = int(x.shape[0]), int(x.shape[1])
+        if B == 0:
+            raise ValueError(f"{what}: no sequences given")
+        n = _lengths(lens, B, f"{what} lengths")
+        if (n < 0).any() or (n > L).any():
+            raise ValueError(f"{what}: lengths {n.tolist()} do not lie in 0 ... {L}")
+        ok = isinstance(x, torch.Tensor) and x.is_cuda and x.device == ctx.device and x.dtype == torch.int32 and x.is_contiguous()
+        t = x.as_subclass(torch.Tensor) if ok else ctx.to_device(x, dtype=torch.int32)
+        if t.numel() == 0:
+            t = ctx.to_device(np.zeros(1, np.int32), dtype=torch.int32)
+        return t, dptr(t), np.arange(B, dtype=np.int64) * L, n, False
+    single = (_is_map(x) and len(x.shape) == 1) or (isinstance(x, (list, tuple)) and all(_is_scalar(v) for v in x))
+    seqs = [x] if single else list(x)
+    if not seqs:
+        raise ValueError(f"{what}: no sequences given")
+    host = []
+    for b, s in enumerate(seqs):
+        if isinstance(s, torch.Tensor):
+            s = s.detach().as_subclass(torch.Tensor).cpu().numpy()
+        a = np.asarray(s)
+        if a.ndim != 1 and a.size:
+            raise ValueError(f"{what} {b}: expected a sequence of ids, got shape {tuple(a.shape)}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{what} {b}: ids are integers, got {a.dtype}")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError(f"{what} {b}: ids are int32")
+        host.append(a.reshape(-1).astype(np.int32))
+    n = np.array([a.size for a in host], dtype=np.int64)
+    flat = np.concatenate(host) if n.sum() else np.zeros(1, np.int32)
+    t = ctx.to_device(flat, dtype=torch.int32)
+    return t, dptr(t), np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64), n, single
+
+
+def _edit_call(ref, hyp, ref_lens, hyp_lens, mode):
+    ctx = Context.get()
+    kr, pr, o_r, n, single = _id_seqs(ctx, ref, ref_lens, "ref")
+    kh, ph, o_h, m, hsingle = _id_seqs(ctx, hyp, hyp_lens, "hyp")
+    if n.size != m.size or single != hsingle:
+        raise ValueError(f"{n.size} sequences ref, {m.size} sequences hyp")
+    B = int(n.size)
+    for b in range(B):
+        if n[b] > EDIT_MAX_TOKENS or m[b] > EDIT_MAX_TOKENS:
+            raise NotImplementedError(f"pair {b} has {int(n[b])} ref ids and {int(m[b])} hyp ids; the engine's envelope is "
+                                      f"0 ... {EDIT_MAX_TOKENS}")
+    if B > EDIT_MAX_BATCH:
+        raise NotImplementedError(f"{B} pairs; the engine's envelope is {EDIT_MAX_BATCH} in a call")
+    n32, m32 = _i32(n), _i32(m)
+    dist = ctx.empty((B,), dtype=torch.int32)
+    po = np.concatenate(([0], np.cumsum(n + m)))
+    counts = ops = ln = None
+    if mode == 1:
+        counts, ln = ctx.empty((B, 4), dtype=torch.int32), ctx.empty((B,), dtype=torch.int32)
+        ops = ctx.empty((max(int(po[-1]), 1),), dtype=torch.uint8)
+    _capi.check(ctx.lib.pk_edit_run(ctx.handle, pr, ph, _p(o_r, C.c_int64), _p(o_h, C.c_int64), _p(n32, C.c_int32),
+                                    _p(m32, C.c_int32), B, int(mode), dptr(dist), None if counts is None else dptr(counts),
+                                    None if ops is None else dptr(ops), None if ln is None else dptr(ln)))
+    d = dist.cpu().numpy()
+    del kr, kh
+    if mode == 0:
+        return int(d[0]) if single else d.astype(np.int64)
+    cn, P = counts.cpu().numpy(), ln.cpu().numpy()
+    out = [EditAlignment(wrap(ops[po[b]:po[b] + P[b]]), d[b], cn[b], P[b], n[b], m[b]) for b in range(B)]
+    return out[0] if single else out
+
+
+def edit_distance(ref, hyp, ref_lens=None, hyp_lens=None):
+    """The Levenshtein distance of token-id sequences (``pk_edit_run``, mode 0: no alignment is kept).  ``ref`` / ``hyp``: one
+    sequence of int32 ids each (a 1-D array, tensor or list of ints), two lists of such, or padded (B, Lmax) tensors with
+    ``ref_lens`` / ``hyp_lens`` (the padding is never read; int32 device tensors are addressed in place).  Empty sequences are
+    valid.  Returns an int for one pair, a (B,) int64 numpy array otherwise.  NotImplementedError outside 0 <= length <= 4096,
+    B <= 65535."""
+    return _edit_call(ref, hyp, ref_lens, hyp_lens, 0)
+
+
+def edit_align(ref, hyp, ref_lens=None, hyp_lens=None):
+    """The distance and the alignment it comes from (``pk_edit_run``, mode 1), inputs as ``edit_distance``.  Returns an
+    ``EditAlignment`` per pair (a list for lists or padded tensors).  Of several minimal edit scripts the one of csrc/pk_edit.h
+    is returned: walking back from the ends, a hit on equal ids, else substitution before deletion before insertion."""
+    return _edit_call(ref, hyp, ref_lens, hyp_lens, 1)
+
+
+def confusions(alignments, refs, hyps):
+    """Host-side tallies over alignments: ``Confusions(substitutions, deletions, insertions)``, three ``Counter`` s keyed by
+    (ref token, hyp token), by the deleted ref token and by the inserted hyp token.  ``refs`` / ``hyps``: the token sequences
+    the ids stood for (any hashable tokens), one per alignment."""
+    if isinstance(alignments, EditAlignment):
+        alignments, refs, hyps = [alignments], [refs], [hyps]
+    if not (len(alignments) == len(refs) == len(hyps)):
+        raise ValueError(f"{len(alignments)} alignments, {len(refs)} references, {len(hyps)} hypotheses")
+    sub, dele, ins = collections.Counter(), collections.Counter(), collections.Counter()
+    for b, (al, r, h) in enumerate(zip(alignments, refs, hyps)):
+        if (al.ref_len, al.hyp_len) != (len(r), len(h)):
+            raise ValueError(f"alignment {b} is one of a {al.ref_len} x {al.hyp_len} pair, the sequences have {len(r)} x {len(h)} tokens")
+        ops = al.ops.as_subclass(torch.Tensor).cpu().numpy()
+        ri, hi = al.index_pairs()
+        for p in np.flatnonzero(ops != HIT):
+            if ops[p] == SUBSTITUTION:
+                sub[(r[ri[p]], h[hi[p]])] += 1
+            elif ops[p] == DELETION:
+                dele[r[ri[p]]] += 1
+            else:
+                ins[h[hi[p]]] += 1
+    return Confusions(sub, dele, ins)

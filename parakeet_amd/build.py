@@ -45,7 +45,7 @@ FILE_FLAGS = {"wf_layer.hip": _UNROLL_ALL, "ffn_planes.hip": _UNROLL_ALL, "ops.h
               "pwg_disc.hip": _NO_SLP, "spk_loss.hip": _NO_SLP, "resample.hip": _NO_SLP, "pitch.hip": _NO_SLP, "align.hip": _NO_SLP, "stats.hip": _NO_SLP,
               "dtw.hip": _NO_SLP + _NO_CONTRACT}
 ISA_DIR = os.path.join(CSRC, "_isa")   # the product build's device assembly, one .s per source (kept for tools/pk_opsel_lint.py and the ISA tools)
-SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
+SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "edit.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
 
 
 def hipcc():

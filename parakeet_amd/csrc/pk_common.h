@@ -155,6 +155,10 @@ struct pk_ctx_scratch {
     pk_dbuf dtw_bits;
     pk_dbuf dtw_carry;
     pk_dbuf dtw_rev;
+    pk_dbuf edit_tab;    // edit.hip: the call's table, the op words that do not fit LDS, the carry rows of pairs of several
+    pk_dbuf edit_bits;   // passes, the reversed ops
+    pk_dbuf edit_carry;
+    pk_dbuf edit_rev;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

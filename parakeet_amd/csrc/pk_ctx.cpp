@@ -95,6 +95,10 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->dtw_bits.release();
         kv.second->dtw_carry.release();
         kv.second->dtw_rev.release();
+        kv.second->edit_tab.release();
+        kv.second->edit_bits.release();
+        kv.second->edit_carry.release();
+        kv.second->edit_rev.release();
         delete kv.second;
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
