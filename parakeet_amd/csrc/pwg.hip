@@ -88,7 +88,26 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #if PK_PWG_SKIP_VEC && PK_PWG_SKIP_SCOPE != 0
 #error "PK_PWG_SKIP_SCOPE measures the dword skip stream: build it with PK_PWG_SKIP_VEC=0"
 #endif
+// The accumulator init of k_pwg_layer_b3 at hop 256 -- acc[co][t] = S1 (bias[co] + sum_j uw_j(t) P[frame + j - 2][co]), the composite 5-tap upsampling
+// filter over the frame-rate projection -- as a 128 x 32 x 6 product on the fp32 matrix pipe.  The 32 samples of a wave tile lie in one frame, so the five
+// staged P rows are the same for all of them: they are the A operand (one float per lane, [co = lane & 31][k = lane >> 5]), with the bias row as the sixth
+// K slot; the lane's own S1 uw[0..4] and S1 itself are the B operand ([k = lane >> 5][sample = lane & 31]).  Four co-tiles x three k-steps = twelve
+// v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate, the first of a co-tile on a zero C) in the accumulator layout stage 1 continues in, instead of 160
+// v_pk_fma_f32, 64 multiplies and twenty 16-byte LDS reads per tile.  The sum is formed in another order than the vector chain's (the bias last, not first):
+// results differ in the last bits.  0 = the vector filter (the A/B: profiles/pwg_aux_mfma_ab.txt).  GEN instantiations (hop != 256: a wave tile can straddle two
+// frames, the A rows would differ by sample) keep the vector filter either way.
+#ifndef PK_PWG_AUX_MFMA
+#define PK_PWG_AUX_MFMA 1
+#endif
 namespace {
+// v, opaque to the optimiser from here on: address arithmetic on it stays where it is written -- not folded into constants, not hoisted out of the tile loop
+// as one loop-invariant register per address
+__device__ __forceinline__ int pwg_opaque(int v) {
+#if defined(__AMDGCN__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
 __device__ __forceinline__ f32x4 pwg_skip_ld4(const float* p) {
 #if PK_PWG_NT_SKIP
     return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
@@ -854,7 +873,8 @@ __device__ __forceinline__ void split_x8s(const float (&v)[8], float s, f16x8& h
 // dependence on the magnitude of weights or activations; |x| beyond 2^113 aside).
 // ABL (profiling only, PK_PWG_ABLATE, results are wrong): 1 = no global loads / stores of x and skip (compute-only time);
 // 2 = the x taps go to the MFMA as loaded, without the hi / lo split (what storing x pre-split would save); 4 / 8 (with 2):
-// the taps loaded as two 16-byte vectors per group instead of eight dwords, in the two candidate planes layouts
+// the taps loaded as two 16-byte vectors per group instead of eight dwords, in the two candidate planes layouts; 16 (the one switch that runs on the planes
+// path, PK_PWG_ABLATE=2048): the accumulator init is the scaled bias alone, no conditioning filter -- the upper bound of what moving the filter can buy
 // PL (HALF only): x lives in HBM as pre-split fp16 planes -- per 32-sample block [octet 8][sample 32][hi 8 | lo 8] halves (the
 // same 8 KB) --, written so by the producer's epilogue, and an operand group is two 16-byte loads that go to the MFMAs as they
 // are: no arithmetic between load and MFMA.  (The scale-and-split of the fp32 taps, 290 of the tile's 1 400 vector
@@ -880,9 +900,10 @@ __device__ __forceinline__ void split_x8s(const float (&v)[8], float s, f16x8& h
 template <bool FIRST, bool HALF, int ABL = 0, bool GEN = false, bool PL = false, bool AMAX = false, bool NZ = false, bool LAST = false>
 __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer_b3(PwgLayerArgs a) {
     static_assert(!NZ || (FIRST && PL && !GEN), "noise-fed: the first block of the planes path at hop 256");
-    static_assert(!PL || (HALF && ABL == 0), "planes: the block-scaled split-fp16 path only");
+    static_assert(!PL || (HALF && (ABL & ~16) == 0), "planes: the block-scaled split-fp16 path only");
     static_assert(!LAST || (HALF && PL && !GEN && !FIRST && !AMAX && !NZ && ABL == 0 && PK_PWG_SKIP_VEC != 0),
                   "fused tail: an ordinary planes block at hop 256 whose skip sum is in accumulator order");
+    constexpr bool AUXM = PK_PWG_AUX_MFMA && !GEN && !(ABL & 16);   // the conditioning filter on the fp32 matrix pipe (PK_PWG_AUX_MFMA above)
     typedef typename Split16<HALF>::vec bf16x8;     // shadows the bf16 typedef inside this kernel
     typedef typename Split16<HALF>::elem elem16;
     constexpr int N_BIAS = LDS_BIAS + (LAST ? SK : 0);
@@ -905,6 +926,9 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
     const int wave = threadIdx.x >> 6;
     const int j = lane & 31;
     const int hi = lane >> 5;
+    // the lane's quad of the stage-2 biases: ONE base register, the constants go into the instructions' offset fields (the bias image lies beyond the 64 KB
+    // an offset field reaches from 0: with the lane term visible hipcc folds it into every constant and keeps sixteen address registers alive across the tile)
+    const float* lds_bias_hi = lds_bias + pwg_opaque(4 * hi);
     const int d = a.dilation;
     const bf16x8* lds_a = reinterpret_cast<const bf16x8*>(lds) + lane;            // + ((ks*2+part)*4+q)*64
     const bf16x8* lds_a2 = reinterpret_cast<const bf16x8*>(lds + LDS_W1) + lane;
@@ -1004,10 +1028,24 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
     };
     bf16x8 ph, pl;     // split operands of the k-step about to run (produced one step ahead, under the MFMAs)
     f32x4 preg[3];
-    float uw[UPW];
+    [[maybe_unused]] f32x2 preg4;   // AUXM: the fifth P row (preg[2] is not used)
+    float uw[AUXM ? 3 : UPW];   // AUXM: the lane's B operands only -- taps hi, 2 + hi and 4
     int df_n = 0;          // GEN: this lane's frame minus the first staged frame (0 / 1) of the tile being prefetched
     bool valid_n = true;   // GEN: the lane's sample lies inside its utterance
     auto prefetch_head = [&](int wt, int cls) {   // cls: edge class of the tile (hop 256), known a tile ahead
+        if constexpr (AUXM) {
+            // the tile's rows from a wave-uniform base plus ONE 32-bit lane offset (wt is wave-uniform, which hipcc cannot see: left alone it keeps a 64-bit
+            // lane address per load alive across the tile); the fifth row as two floats per lane, every lane
+            const float* prow = a.P + (long)(__builtin_amdgcn_readfirstlane(wt >> 3) - 2) * a.ldp;
+            const int lt = pwg_opaque(lane);   // (the offsets are formed per tile from the lane number, not kept as loop invariants)
+            const unsigned lo = (unsigned)((lt >> 5) * a.ldp + 4 * (lt & 31));
+            preg[0] = *reinterpret_cast<const f32x4*>(prow + lo);
+            preg[1] = *reinterpret_cast<const f32x4*>(prow + 2 * a.ldp + lo);
+            preg4 = *reinterpret_cast<const f32x2*>(prow + 4 * a.ldp + (unsigned)(2 * lt));
+            // the lane's B operands: taps hi, 2 + hi, 4 + hi (lane half 1 reads the row's zero padding behind tap 4: S1 stands there where it is used)
+            const float* wrow = a.uptab + (unsigned)((cls * TILE + (wt & 7) * WAVE_T + (lt & 31)) * UPW_PAD + (lt >> 5));
+            uw[0] = wrow[0]; uw[1] = wrow[2]; uw[2] = wrow[4];
+        } else {
         const int tile = wt >> 3, phase = (wt & 7) * WAVE_T + j;
         const float* prow;
         long wsel;   // row of the upsampler table: edge class * hop + phase
@@ -1031,6 +1069,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         const f32x4 w0 = *reinterpret_cast<const f32x4*>(wrow);
         uw[0] = w0[0]; uw[1] = w0[1]; uw[2] = w0[2]; uw[3] = w0[3];
         uw[4] = wrow[4];
+        }
     };
     // NZ: the lane's noise at t - 1, t, t + 1 of the NEXT tile (requested a tile ahead, like t0n), and the edge class of the current tile
     float nzn[3] = {0.f, 0.f, 0.f};
@@ -1122,10 +1161,11 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
         }
         // [wave-lds-exchange] every lane of the wave has finished reading the previous tile's rows out of lds_p
 #pragma unroll
-        for (int it = 0; it < 3; ++it) {
+        for (int it = 0; it < (AUXM ? 2 : 3); ++it) {
             const int idx = lane + 64 * it;
             if (idx < (UPW + (GEN ? 1 : 0)) * (G / 4)) reinterpret_cast<f32x4*>(lds_p)[idx] = preg[it];
         }
+        if constexpr (AUXM) reinterpret_cast<f32x2*>(lds_p + 4 * G)[lane] = preg4;
         // [wave-lds-exchange] the rows are read below by OTHER lanes of the same wave (a wave's LDS instructions execute in
         // order for all its lanes, so the hardware needs no barrier here; tools/hipemu turns these markers into a rendezvous)
         const bool lane_valid = valid_n;                 // of THIS tile (prefetch_head(next) overwrites valid_n)
@@ -1138,13 +1178,29 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
             sx = pow2f(kx);
             const float S1 = pow2f(ks1);
 #pragma unroll
-            for (int jj = 0; jj < UPW; ++jj) uw[jj] *= S1;
+            for (int jj = 0; jj < (AUXM ? 3 : UPW); ++jj) uw[jj] *= S1;
             const int cbb = __builtin_amdgcn_readfirstlane(__float_as_int(-1.4426950408889634f * pow2f(-ks1)));
             gcb = __int_as_float(cbb);
             gca = __int_as_float(cbb + (1 << 23));   // 2 * gcb
         }
         const float S1b = HALF ? pow2f(kx + a.k1) : 1.f;
         f32x16 acc[4];
+        if constexpr (AUXM) {
+            // the filter on the fp32 matrix pipe (PK_PWG_AUX_MFMA above): k-step m multiplies rows 2 m + hi of the staged P (the bias for m = 2, hi = 1: the sixth
+            // K slot) with the lane's S1 uw[2 m + hi] (S1 itself there).  A lane reads one float per MFMA, consecutive lanes consecutive words
+            static_assert(UPW == 5, "three k-steps of two: five taps and the bias");
+            const int lt = pwg_opaque(lane);   // (formed per tile from the lane number: as loop invariants these addresses cost three registers across the tile)
+            const float* a_p = lds_p + (lt >> 5) * G + (lt & 31);
+            const float* a_b = (lt >> 5) ? lds_bias + (lt & 31) : lds_p + 4 * G + (lt & 31);
+            const float b0 = uw[0], b1 = uw[1], b2 = hi ? S1b : uw[2];
+            const f32x16 z16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_p[32 * q], b0, z16, 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_p[2 * G + 32 * q], b1, acc[q], 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_b[32 * q], b2, acc[q], 0, 0, 0);
+        } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -1153,7 +1209,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
                 f32x4 v = *reinterpret_cast<const f32x4*>(lds_bias + co0);
                 if constexpr (HALF) v *= S1b;
 #pragma unroll
-                for (int jj = 0; jj < UPW; ++jj) {
+                for (int jj = 0; jj < ((ABL & 16) ? 0 : UPW); ++jj) {   // ABL 16: the scaled bias alone, no filter
                     const f32x4 pv = *reinterpret_cast<const f32x4*>(lds_pl + jj * G + co0);
                     v[0] = fmaf(uw[jj], pv[0], v[0]);
                     v[1] = fmaf(uw[jj], pv[1], v[1]);
@@ -1165,6 +1221,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
                 acc[q][4 * r4 + 2] = v[2];
                 acc[q][4 * r4 + 3] = v[3];
             }
+        }
 
         // stage 1: 12 k-steps.  Step g: refill the free ring slot with group g+RING, then run the 12 MFMAs of
         // group g while the VALU splits group g+1 (sched_group_barrier interleaves them: a 32x32x16 MFMA
@@ -1328,7 +1385,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
             for (int q = 0; q < 2; ++q)
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias + G + 64 + 32 * q + 8 * r4 + 4 * hi);
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias_hi + G + 64 + 32 * q + 8 * r4);
                     acc2[q][4 * r4 + 0] = bv[0];
                     acc2[q][4 * r4 + 1] = bv[1];
                     acc2[q][4 * r4 + 2] = bv[2];
@@ -1381,7 +1438,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
             for (int q = 0; q < 2; ++q)
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias + G + 32 * q + 8 * r4 + 4 * hi);   // last_conv_layers.1.bias
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(lds_bias_hi + G + 32 * q + 8 * r4);   // last_conv_layers.1.bias
                     acc3[q][4 * r4 + 0] = bv[0] * Sl;
                     acc3[q][4 * r4 + 1] = bv[1] * Sl;
                     acc3[q][4 * r4 + 2] = bv[2] * Sl;
@@ -1420,7 +1477,7 @@ __global__ __launch_bounds__(LAYER_WAVES * 64, LAYER_WAVES / 4) void k_pwg_layer
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const f32x4 bv =
-                        *reinterpret_cast<const f32x4*>(lds_bias + G + 64 * pass + 32 * q + 8 * r4 + 4 * hi);
+                        *reinterpret_cast<const f32x4*>(lds_bias_hi + G + 64 * pass + 32 * q + 8 * r4);
                     acc2[q][4 * r4 + 0] = bv[0];
                     acc2[q][4 * r4 + 1] = bv[1];
                     acc2[q][4 * r4 + 2] = bv[2];
@@ -1832,6 +1889,7 @@ static int pwg_ablation_launch(pk_ctx* ctx, int dbg, int grid, dim3 blk, const P
         else if (dbg == 32) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 2>), dim3(grid), blk, 0, a);
         else if (dbg == 96) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 6>), dim3(grid), blk, 0, a);
         else if (dbg == 160) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 10>), dim3(grid), blk, 0, a);
+        else if (dbg == 2048) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 16, false, true>), dim3(grid), blk, 0, a);   // planes, no filter
         else PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true>), dim3(grid), blk, 0, a);
         return PK_OK;
     } else {
@@ -2608,7 +2666,8 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
     // (profile build: PK_PWG_ABLATE=1024 runs every layer on the FIRST kernel -- skip written, never read: the skip sum and the
     // waveform are wrong, x and the gates are not -- to measure what 256 of the 1 024 B per sample and layer cost)
     const bool all_first = PK_PROFILE_BUILD != 0 && h->dbg == 1024;
-    bool planes = h->planes_on && h->math == PK_PWG_MATH_F16X3 && (h->dbg == 0 || all_first) && (size_t)R * Ttot * 4 < ((size_t)1 << 32);
+    const bool no_filter = PK_PROFILE_BUILD != 0 && h->dbg == 2048;   // PK_PWG_ABLATE=2048: the ordinary planes blocks without the conditioning filter
+    bool planes = h->planes_on && h->math == PK_PWG_MATH_F16X3 && (h->dbg == 0 || all_first || no_filter) && (size_t)R * Ttot * 4 < ((size_t)1 << 32);
     // a guarded inference (option "scale_guard") measures max|x| per utterance and layer next to the a-priori bound; should
     // the bound overshoot by more than 2^GUARD_MAX_LOG2 the stack is run again on the fp32-x path (second pass of this loop:
     // the noise, the conditioning P and the zeroed gaps are all still in place), which the handle then keeps
@@ -2778,6 +2837,7 @@ extern "C" int pk_pwg_infer(pk_pwg* h, const float* mel, const int32_t* frames, 
                         PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, false, true, false, false, true>), dim3(grid), blk, 0, a);
                     } else {
                         if (l == 0 || all_first) PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<true, true, 0, false, true>), dim3(grid), blk, 0, a);
+                        else if (no_filter) PK_TRY(pwg_ablation_launch<PK_PROFILE_BUILD != 0>(ctx, h->dbg, grid, blk, a));
                         else PK_LAUNCH(ctx, "pwg_layer_h3", (k_pwg_layer_b3<false, true, 0, false, true>), dim3(grid), blk, 0, a);
                     }
                 } else if (gen) {   // hop != 256: frame / phase per sample (GEN kernels)

@@ -10,6 +10,7 @@ if mode == "pwg":
     from parakeet_amd.parallel_wavegan import PWGGenerator
     gen = PWGGenerator(**syn.PWG_LJSPEECH); gen.set_state_dict(syn.pwg_state()); gen.eval()
     gen.set_option("scale_guard", 0)   # the ONE call of this script would be the guarded first call: count the instantiation every other call runs
+    if os.environ.get("PK_QPWG_TAIL"): gen.set_option("fused_tail", int(os.environ["PK_QPWG_TAIL"]))   # 0: k_pwg_last_h3 runs -- pmc_traffic.py calibrates FETCH_SIZE on it
     rng = np.random.default_rng(42)
     mels = [torch.tensor(rng.normal(size=(L, 80)).astype(np.float32)).cuda() for _ in range(B)]
     noises = [torch.randn(L * 256, device="cuda") for _ in range(B)]
