@@ -37,6 +37,8 @@ def parse_args(argv=None):
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--linear", action="store_true", help="the mels are linear magnitudes, not natural logs")
     ap.add_argument("--bins-first", action="store_true", help="the files hold (n_mels, frames)")
+    ap.add_argument("--transform", choices=("dense", "fft"), default="dense",
+                    help="fft: run the STFT and its inverse on the radix FFT (n_fft a power of two from 32 to 4096)")
     return ap.parse_args(argv)
 
 
@@ -44,7 +46,7 @@ def main(argv=None):
     args = parse_args(argv)
     from parakeet_amd.audio import AudioProcessor, GriffinLim, LogMagnitude
     proc = AudioProcessor(args.sample_rate, args.n_fft, args.win_length, args.hop_length, n_mels=args.n_mels,
-                          fmin=args.fmin, fmax=args.fmax)
+                          fmin=args.fmin, fmax=args.fmax, transform=args.transform)
     voc = GriffinLim(proc, None if args.linear else LogMagnitude(), n_iter=args.n_iter, momentum=args.momentum,
                      power=args.power)
     names = sorted(f for f in os.listdir(args.input_dir) if f.endswith(".npy"))

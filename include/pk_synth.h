@@ -713,7 +713,26 @@ int pk_mel_num_frames(pk_mel* h, int32_t n_samples, int32_t* frames);
  *    that reads the frame's spectrum. */
 int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int32_t B, float* out,
                int32_t what, int32_t flags);
+/* How the handle transforms its frames.  PK_TRANSFORM_DENSE (the default): the product with the windowed DFT basis.
+ * PK_TRANSFORM_FFT: the radix FFT of csrc/rfft.hip -- frame * window in fp32, then the transform; the re | im rows of
+ * what 0 - 3 come from it, every later stage is the same.  Timeline rows that belong to no frame are skipped for what 0.
+ * n_fft must be a power of two from 32 to 4096, else PK_EUNSUPPORTED (the handle keeps its transform); another value of
+ * `transform`: PK_EINVAL. */
+#define PK_TRANSFORM_DENSE 0
+#define PK_TRANSFORM_FFT 1
+int pk_mel_set_transform(pk_mel* h, int32_t transform);
 void pk_mel_destroy(pk_mel* h);
+/* The radix FFT as a primitive (csrc/rfft.hip, plan and rounding count in csrc/pk_rfft.h): numpy.fft.rfft / irfft of
+ * `rows` rows of n real points, n a power of two from 32 to 4096 (pk_rfft_supported: 1, else 0; another n:
+ * PK_EUNSUPPORTED).  x (rows, n) and out (rows, n + 2) = re (n/2 + 1) | im (n/2 + 1) per row, the layout of
+ * pk_mel_run(what = 0); pk_op_irfft reads that layout and writes (rows, n), ignoring im(DC) and im(Nyquist) as numpy does
+ * and scaling by 1/n.  DEVICE pointers, 8-byte aligned; enqueued on the context's stream (the first call for an n uploads
+ * its twiddle table and synchronises).  One workgroup transforms pk_rfft_tile_rows(n) whole rows; a row's result is the
+ * same bits wherever it stands in a batch. */
+int pk_rfft_supported(int32_t n);
+int pk_rfft_tile_rows(int32_t n, int32_t* rows);
+int pk_op_rfft(pk_ctx* ctx, const float* x, int64_t rows, int32_t n, float* out);
+int pk_op_irfft(pk_ctx* ctx, const float* spec, int64_t rows, int32_t n, float* out);
 /* Token averages of frame-level features (get_feats.py _average_by_duration :141-153, :205-214):
  * out[t] = mean(x[cum[t-1]:cum[t]]) over the frames of token t, 0 for a token of 0 frames; spans are cut at `frames`
  * like a numpy slice.  x: DEVICE (frames, C); durations: HOST (T), >= 0; out: DEVICE (T, C).  Synchronises. */
@@ -765,6 +784,11 @@ int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int32_t* frames
  * 0 = the spectrum the last iteration's forward STFT rebuilt (PK_ESTATE after n_iter = 0), 1 = the last iterate
  * mag * angles, the spectrum the returned waveform is the ISTFT of. */
 int pk_gl_debug_read(pk_istft* h, int32_t what, float* out, int64_t n);
+/* PK_TRANSFORM_DENSE (default) or PK_TRANSFORM_FFT, as pk_mel_set_transform: under FFT every frame is the inverse radix
+ * FFT of its re | im row (read where the caller left it), times the window; overlap-add and everything else are the
+ * same kernels.  pk_gl_run needs both handles on the same transform (else PK_EINVAL) and then runs both directions of its
+ * loop on it; n_iter = 0 stays pk_istft_run of mag * angles, bit for bit, on that transform. */
+int pk_istft_set_transform(pk_istft* h, int32_t transform);
 void pk_istft_destroy(pk_istft* h);
 
 /* ------------------------------------------------------------- resampling */

@@ -32,6 +32,8 @@ PK_TRIM_SCAN_CHUNK = 256
 PK_TRIM_PAD = {None: 0, "reflect": 1, "constant": 2}
 # csrc/pk_stats.h: the envelope of pk_stats_*; pk_stats_update's flag
 PK_STATS_MAX_DIM, PK_STATS_MAX_ROWS, PK_STATS_MOMENTS_ONLY = 1024, 2 ** 31 - 1, 1
+# pk_mel_set_transform / pk_istft_set_transform
+PK_TRANSFORM = {"dense": 0, "fft": 1}
 _EXC = {
     -1: ValueError,
     -2: AssertionError,
@@ -270,12 +272,18 @@ def _declare(lib):
         "pk_mel_create": (C.c_int, [vp, C.POINTER(MelCfg), f32p, f32p, C.POINTER(vp)]),
         "pk_mel_num_frames": (C.c_int, [vp, i32, i32p]),
         "pk_mel_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32, i32]),
+        "pk_mel_set_transform": (C.c_int, [vp, i32]),
         "pk_mel_destroy": (None, [vp]),
+        "pk_rfft_supported": (C.c_int, [i32]),
+        "pk_rfft_tile_rows": (C.c_int, [i32, i32p]),
+        "pk_op_rfft": (C.c_int, [vp, f32p, i64, i32, f32p]),
+        "pk_op_irfft": (C.c_int, [vp, f32p, i64, i32, f32p]),
         "pk_istft_create": (C.c_int, [vp, C.POINTER(IstftCfg), f32p, C.POINTER(vp)]),
         "pk_istft_num_samples": (C.c_int, [vp, i32, i32p]),
         "pk_istft_run": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
         "pk_gl_run": (C.c_int, [vp, vp, f32p, i32p, i32, i32, C.c_float, C.POINTER(C.c_uint64), f32p, f32p, i32]),
         "pk_gl_debug_read": (C.c_int, [vp, i32, f32p, i64]),
+        "pk_istft_set_transform": (C.c_int, [vp, i32]),
         "pk_istft_destroy": (None, [vp]),
         "pk_resample_create": (C.c_int, [vp, C.POINTER(ResampleCfg), f32p, C.POINTER(vp)]),
         "pk_resample_out_len": (C.c_int, [vp, i64, i64p]),

@@ -11,6 +11,10 @@ The way back -- ``ISTFT``, ``AudioProcessor.stft`` / ``istft`` / ``griffin_lim``
 ``GriffinLim`` vocoder -- follows parakeet/audio/audio.py:75-93 (librosa's ``istft``) and ``librosa.griffinlim``; it runs in
 csrc/istft.hip.
 
+``rfft`` / ``irfft``: the radix FFT of csrc/rfft.hip as a primitive.  ``transform="fft"`` on ``STFT``, ``ISTFT``,
+``LogMelFBank`` and ``AudioProcessor`` (and through it ``GriffinLim``) runs their frames on it instead of the dense DFT
+products (the default, ``"dense"``); it needs an n_fft that is a power of two from 32 to 4096.
+
 ``resample_filter`` / ``Resample`` / ``resample`` / ``load_wav`` put audio of any rate on the model's rate: a polyphase
 Kaiser-windowed sinc defined in DESIGN.md 4.5d (this project's own filter; the reference calls ``librosa.load(path, sr=fs)``,
 whose resampler is not available here and is not reproduced), run by csrc/resample.hip.
@@ -65,8 +69,66 @@ def _window(window, win_length, n_fft):
     return np.ascontiguousarray(w, dtype=np.float32)
 
 
+def _transform_id(transform):
+    if transform not in _capi.PK_TRANSFORM:
+        raise ValueError(f"transform must be 'dense' or 'fft', got {transform!r}")
+    return _capi.PK_TRANSFORM[transform]
+
+
+def rfft_supported(n):
+    """True where the radix FFT takes n points: a power of two from 32 to 4096."""
+    return bool(_capi.lib().pk_rfft_supported(int(n)))
+
+
+def rfft_tile_rows(n):
+    """Rows one workgroup of the FFT kernels transforms at n points."""
+    r = C.c_int32()
+    _capi.check(_capi.lib().pk_rfft_tile_rows(int(n), C.byref(r)))
+    return r.value
+
+
+def rfft(x, as_complex=False, device=None):
+    """``numpy.fft.rfft`` of the rows of x (rows, n) on the engine's radix FFT (csrc/rfft.hip), n a power of two from 32 to
+    4096.  Returns a (rows, n + 2) device tensor re | im per row, the layout of ``pk_mel_run(what=0)``; with
+    ``as_complex`` a complex64 (rows, n/2 + 1) tensor."""
+    ctx = Context.get(device)
+    x = ctx.to_device(x)
+    if x.dim() != 2:
+        raise AssertionError(f"rfft: expected (rows, n), got {tuple(x.shape)}")
+    x = x.contiguous()
+    rows, n = x.shape
+    out = ctx.empty((rows, n + 2))
+    _capi.check(ctx.lib.pk_op_rfft(ctx.handle, dptr(x), rows, n, dptr(out)))
+    if as_complex:
+        return wrap(torch.complex(out[:, :n // 2 + 1], out[:, n // 2 + 1:]))
+    return wrap(out)
+
+
+def irfft(spec, n=None, device=None):
+    """``numpy.fft.irfft`` of the rows of spec: (rows, n + 2) re | im or complex (rows, n/2 + 1) -> (rows, n) device tensor.
+    The imaginary parts of DC and Nyquist are ignored.  ``n`` may be given to check it; it follows from the shape."""
+    ctx = Context.get(device)
+    if isinstance(spec, np.ndarray) and np.iscomplexobj(spec):
+        spec = np.concatenate([spec.real, spec.imag], axis=1).astype(np.float32)
+    elif isinstance(spec, torch.Tensor) and spec.is_complex():
+        spec = torch.cat([spec.real, spec.imag], dim=1).to(torch.float32)
+    spec = ctx.to_device(spec)
+    if spec.dim() != 2 or spec.shape[1] < 4 or spec.shape[1] % 2:
+        raise AssertionError(f"irfft: expected (rows, n + 2) re | im or complex (rows, n/2 + 1), got {tuple(spec.shape)}")
+    spec = spec.contiguous()
+    rows, m = spec.shape[0], spec.shape[1] - 2
+    if n is not None and int(n) != m:
+        raise AssertionError(f"irfft: the rows hold the spectrum of {m} points, n = {n} was asked for")
+    out = ctx.empty((rows, m))
+    _capi.check(ctx.lib.pk_op_irfft(ctx.handle, dptr(spec), rows, m, dptr(out)))
+    return wrap(out)
+
+
 class _Engine:
-    def __init__(self, n_fft, hop_length, win_length, window, center, power, mel_basis, log_base, device=None):
+    def __init__(self, n_fft, hop_length, win_length, window, center, power, mel_basis, log_base, device=None,
+                 transform="dense"):
+        tid = _transform_id(transform)
+        self.transform = transform
         self.ctx = Context.get(device)
         cfg = _capi.MelCfg(n_fft, hop_length, 1 if center else 0, 1 if power else 0,
                            0 if mel_basis is None else mel_basis.shape[0], log_base, 1e-10)
@@ -78,6 +140,8 @@ class _Engine:
         _capi.check(self.ctx.lib.pk_mel_create(self.ctx.handle, C.byref(cfg), _capi.fptr(win),
                                                None if basis is None else _capi.fptr(basis), C.byref(h)))
         self.h = h
+        if tid:
+            _capi.check(self.ctx.lib.pk_mel_set_transform(h, tid))
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -112,15 +176,17 @@ class _Engine:
 class STFT:
     """(B, T) -> real, imag (B, n_bin, frames); audio.py:74-215."""
 
-    def __init__(self, n_fft, hop_length=None, win_length=None, window="hanning", center=True, pad_mode="reflect"):
+    def __init__(self, n_fft, hop_length=None, win_length=None, window="hanning", center=True, pad_mode="reflect",
+                 transform="dense"):
         if pad_mode != "reflect":
             raise NotImplementedError("only pad_mode='reflect' is implemented")
         win_length = win_length or n_fft
         hop_length = hop_length or int(win_length // 4)
         self.n_fft, self.hop_length, self.n_bin, self.center = n_fft, hop_length, 1 + n_fft // 2, center
-        self._mag = _Engine(n_fft, hop_length, win_length, window, center, False, None, 0)
+        self._mag = _Engine(n_fft, hop_length, win_length, window, center, False, None, 0, transform=transform)
         self._pow = None
         self._args = (n_fft, hop_length, win_length, window, center)
+        self.transform = transform
 
     def _batch(self, x, eng, what):
         x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
@@ -136,7 +202,7 @@ class STFT:
     def power(self, x):
         if self._pow is None:
             n_fft, hop, win, window, center = self._args
-            self._pow = _Engine(n_fft, hop, win, window, center, True, None, 0)
+            self._pow = _Engine(n_fft, hop, win, window, center, True, None, 0, transform=self.transform)
         return wrap(self._batch(x, self._pow, 1))
 
     def magnitude(self, x):
@@ -146,7 +212,9 @@ class STFT:
 class _InvEngine:
     """A pk_istft handle: packed (frames, 2*n_bin) re | im rows -> samples, and the Griffin-Lim loop around it."""
 
-    def __init__(self, n_fft, hop_length, win_length, window, center, device=None):
+    def __init__(self, n_fft, hop_length, win_length, window, center, device=None, transform="dense"):
+        tid = _transform_id(transform)
+        self.transform = transform
         self.ctx = Context.get(device)
         cfg = _capi.IstftCfg(n_fft, hop_length, 1 if center else 0)
         self.n_fft, self.n_bin = n_fft, 1 + n_fft // 2
@@ -154,6 +222,8 @@ class _InvEngine:
         h = C.c_void_p()
         _capi.check(self.ctx.lib.pk_istft_create(self.ctx.handle, C.byref(cfg), _capi.fptr(win), C.byref(h)))
         self.h = h
+        if tid:
+            _capi.check(self.ctx.lib.pk_istft_set_transform(h, tid))
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -221,11 +291,11 @@ class _InvEngine:
 class ISTFT:
     """real, imag (B, n_bin, frames) -> (B, T): the inverse of ``STFT`` (librosa's ``istft``, audio.py:86-93)."""
 
-    def __init__(self, n_fft, hop_length=None, win_length=None, window="hanning", center=True):
+    def __init__(self, n_fft, hop_length=None, win_length=None, window="hanning", center=True, transform="dense"):
         win_length = win_length or n_fft
         hop_length = hop_length or int(win_length // 4)
         self.n_fft, self.hop_length, self.n_bin, self.center = n_fft, hop_length, 1 + n_fft // 2, center
-        self._eng = _InvEngine(n_fft, hop_length, win_length, window, center)
+        self._eng = _InvEngine(n_fft, hop_length, win_length, window, center, transform=transform)
 
     def forward(self, real, imag):
         ctx = Context.get()
@@ -274,7 +344,9 @@ class LogMelFBank:
     """get_feats.py:20-88 on the device: wav -> (num_frames, n_mels) log-mel."""
 
     def __init__(self, sr=24000, n_fft=2048, hop_length=300, win_length=None, window="hann", n_mels=80,
-                 fmin=80, fmax=7600, eps=1e-10):
+                 fmin=80, fmax=7600, eps=1e-10, transform="dense"):
+        _transform_id(transform)
+        self.transform = transform
         self.sr, self.n_fft, self.hop_length = sr, n_fft, hop_length
         self.fmin = 0 if fmin is None else fmin
         self.fmax = sr / 2 if fmax is None else fmax
@@ -286,7 +358,7 @@ class LogMelFBank:
         if base not in self._eng:
             n_fft, hop, win, window = self._args
             self._eng[base] = _Engine(n_fft, hop, win, window, True, False, self.mel_filter,
-                                      10 if base == "10" else 2)
+                                      10 if base == "10" else 2, transform=self.transform)
         return self._eng[base]
 
     def get_log_mel_fbank(self, wav, base="10", sr=None):
@@ -1192,17 +1264,18 @@ class AudioProcessor:
     another rate is resampled to the processor's on the engine, where the reference resamples with librosa."""
 
     def __init__(self, sample_rate, n_fft, win_length, hop_length, n_mels=80, fmin=0, fmax=None, window="hann",
-                 center=True, pad_mode="reflect", normalize=True):
+                 center=True, pad_mode="reflect", normalize=True, transform="dense"):
         if pad_mode != "reflect":
             raise NotImplementedError("only pad_mode='reflect' is implemented")
+        self.transform = transform
         self.sample_rate, self.normalize = sample_rate, normalize
         self.n_fft, self.win_length, self.hop_length = n_fft, win_length, hop_length
         self.window, self.center, self.pad_mode = window, center, pad_mode
         self.n_mels, self.fmin, self.fmax = n_mels, fmin, fmax
         self.mel_filter = mel_filterbank(sample_rate, n_fft, n_mels, fmin or 0, fmax or sample_rate / 2)
         self.inv_mel_filter = np.linalg.pinv(self.mel_filter)
-        self._spec = _Engine(n_fft, hop_length, win_length, window, center, False, None, 0)
-        self._mel = _Engine(n_fft, hop_length, win_length, window, center, False, self.mel_filter, 0)
+        self._spec = _Engine(n_fft, hop_length, win_length, window, center, False, None, 0, transform=transform)
+        self._mel = _Engine(n_fft, hop_length, win_length, window, center, False, self.mel_filter, 0, transform=transform)
         self._inv = None
 
     def read_wav(self, filename):
@@ -1228,7 +1301,8 @@ class AudioProcessor:
 
     def _inverse(self):
         if self._inv is None:
-            self._inv = _InvEngine(self.n_fft, self.hop_length, self.win_length, self.window, self.center)
+            self._inv = _InvEngine(self.n_fft, self.hop_length, self.win_length, self.window, self.center,
+                                   transform=self.transform)
         return self._inv
 
     @staticmethod

@@ -10,6 +10,9 @@
 // buffer; k_istft_ola GATHERS it: a thread owns four consecutive output samples and adds up the at most ceil(n_fft / hop)
 // frames that overlap them in ascending frame order -- no atomics, a fixed order, nothing shared between utterances, so an
 // utterance's samples do not depend on the batch they are computed in.
+//
+// Under PK_TRANSFORM_FFT (pk_istft_set_transform) the frame buffer comes from the inverse radix FFT of rfft.hip instead of the
+// product, and the Griffin-Lim loop's forward transform from its forward kernel; every other kernel here is the same.
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -18,6 +21,7 @@
 #include "pk_mel.h"
 #include "pk_mfma.h"
 #include "pk_philox.h"
+#include "pk_rfft.h"
 
 namespace {
 
@@ -143,6 +147,7 @@ struct pk_istft {
     pk_ctx* ctx = nullptr;
     pk_istft_cfg cfg;
     int n_bin = 0, K = 0;
+    int transform = PK_TRANSFORM_DENSE;
     pk_dbuf d_basis, d_window;
     pk_dbuf ws_tab, ws_itab, ws_in, ws_in2, ws_out, ws_A, ws_frames, ws_xpad, ws_r[2];
     long last_rows = 0;   // pk_gl_debug_read: frames of the last pk_gl_run and the buffer its last forward STFT wrote (-1: none)
@@ -178,23 +183,29 @@ int make_layout(const pk_istft* h, const int32_t* frames, int B, const char* who
     return PK_OK;
 }
 
-// frames = A . basis, then the gather into `out` (tab[b].ooff); A holds sumF rows of K floats
+// frames = A . basis, then the gather into `out` (tab[b].ooff); A holds sumF rows of K floats.  Under PK_TRANSFORM_FFT the
+// frames are the inverse radix FFT of the rows at `spec` (leading dimension ld), times the window: A or the caller's spectrum
 int synth_and_ola(pk_istft* h, long sumF, const istft_utt* d_tab, int B, int maxlen, float* out, const char* gemm_name,
-                  const char* ola_name) {
+                  const char* ola_name, const float* spec = nullptr, long ld = 0) {
     pk_ctx* ctx = h->ctx;
     const int N = h->cfg.n_fft, hop = h->cfg.hop_length;
-    pk_gemm_args g;
-    g.A = h->ws_A.as<float>();
-    g.lda = h->K;
-    g.Cin = h->K;
-    g.taps = 1;
-    g.pad = 0;
-    g.Wp = h->d_basis.as<float>();
-    g.M = (int)sumF;
-    g.N = N;
-    g.C = h->ws_frames.as<float>();
-    g.ldc = N;
-    PK_TRY(pk_gemm_launch(ctx, gemm_name, g));
+    if (h->transform == PK_TRANSFORM_FFT) {
+        PK_TRY(pk_rfft_inverse(ctx, gemm_name, spec ? spec : h->ws_A.as<float>(), spec ? ld : (long)h->K,
+                               h->d_window.as<float>(), sumF, N, h->ws_frames.as<float>()));
+    } else {
+        pk_gemm_args g;
+        g.A = h->ws_A.as<float>();
+        g.lda = h->K;
+        g.Cin = h->K;
+        g.taps = 1;
+        g.pad = 0;
+        g.Wp = h->d_basis.as<float>();
+        g.M = (int)sumF;
+        g.N = N;
+        g.C = h->ws_frames.as<float>();
+        g.ldc = N;
+        PK_TRY(pk_gemm_launch(ctx, gemm_name, g));
+    }
     if (maxlen > 0) {
         const int vec = ((uintptr_t)out % 16) == 0 ? 1 : 0;
         PK_LAUNCH(ctx, ola_name, k_istft_ola, dim3(pk_div_up(maxlen, OLA_BLOCK * OLA_SPT), B), dim3(OLA_BLOCK),
@@ -281,9 +292,15 @@ extern "C" int pk_istft_run(pk_istft* h, const float* spec, const int32_t* frame
         d_out = h->ws_out.as<float>();
     }
     PK_TRY(reserve_product(h, L.sumF));
-    PK_LAUNCH(ctx, "istft_pack", k_istft_pack, dim3((unsigned)L.sumF, pk_div_up(h->K, 256)), dim3(256), 0, d_spec, nb,
-              h->ws_A.as<float>(), h->K);
-    PK_TRY(synth_and_ola(h, L.sumF, h->ws_tab.as<istft_utt>(), B, L.maxlen, d_out, "istft_gemm", "istft_ola"));
+    if (h->transform == PK_TRANSFORM_FFT) {
+        // the inverse FFT reads the caller's rows where they are and never looks at im(DC), im(Nyquist): nothing to pack
+        PK_TRY(synth_and_ola(h, L.sumF, h->ws_tab.as<istft_utt>(), B, L.maxlen, d_out, "istft_fft", "istft_ola", d_spec,
+                             2 * nb));
+    } else {
+        PK_LAUNCH(ctx, "istft_pack", k_istft_pack, dim3((unsigned)L.sumF, pk_div_up(h->K, 256)), dim3(256), 0, d_spec, nb,
+                  h->ws_A.as<float>(), h->K);
+        PK_TRY(synth_and_ola(h, L.sumF, h->ws_tab.as<istft_utt>(), B, L.maxlen, d_out, "istft_gemm", "istft_ola"));
+    }
     if (flags & PK_HOST_IO) {
         if (L.sumS > 0) PK_HIP(hipMemcpyAsync(wav_out, d_out, (size_t)L.sumS * 4, hipMemcpyDeviceToHost, ctx->stream));
         PK_HIP(hipStreamSynchronize(ctx->stream));
@@ -303,6 +320,10 @@ extern "C" int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int3
         PK_FAIL(PK_EINVAL, "pk_gl_run: the STFT handle (n_fft %d, hop %d, center %d) does not match the ISTFT handle (%d, %d, %d)",
                 (int)mc.n_fft, (int)mc.hop_length, (int)mc.center, (int)c.n_fft, (int)c.hop_length, (int)c.center);
     if (pk_mel_context(stft) != h->ctx) PK_FAIL(PK_EINVAL, "pk_gl_run: the two handles belong to different contexts");
+    if (pk_mel_transform(stft) != h->transform)
+        PK_FAIL(PK_EINVAL, "pk_gl_run: the STFT handle's transform (%d) differs from the ISTFT handle's (%d); set both with "
+                "pk_mel_set_transform / pk_istft_set_transform", pk_mel_transform(stft), h->transform);
+    const bool fft = h->transform == PK_TRANSFORM_FFT;
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     istft_layout L;
@@ -398,22 +419,42 @@ extern "C" int pk_gl_run(pk_istft* h, pk_mel* stft, const float* mag, const int3
         const float coef = momentum / (1.f + momentum);
         // every iteration is enqueued on the stream; the host does not wait inside the loop
         for (int it = 0; it < n_iter; ++it) {
-            PK_TRY(synth_and_ola(h, L.sumF, d_tab, B, L.maxlen, h->ws_xpad.as<float>(), "gl_istft_gemm", "gl_istft_ola"));
+            PK_TRY(synth_and_ola(h, L.sumF, d_tab, B, L.maxlen, h->ws_xpad.as<float>(), fft ? "gl_istft_fft" : "gl_istft_gemm",
+                                 "gl_istft_ola"));
             if (pad > 0)
                 PK_LAUNCH(ctx, "gl_reflect", k_gl_reflect_edges, dim3(pk_div_up(2 * pad, 256), B), dim3(256), 0,
                           h->ws_xpad.as<float>(), d_tab, hop, pad);
             g.C = h->ws_r[it & 1].as<float>();
-            PK_TRY(pk_gemm_launch(ctx, "gl_stft_gemm", g));
+            if (fft)
+                PK_TRY(pk_rfft_forward(ctx, "gl_stft_fft", g.A, hop, pk_mel_window(stft), d_rowmap, rows, N, g.C, g.ldc));
+            else
+                PK_TRY(pk_gemm_launch(ctx, "gl_stft_gemm", g));
             PK_LAUNCH(ctx, "gl_phase", k_gl_phase, egrid, dim3(256), 0, h->ws_r[it & 1].as<float>(),
                       it > 0 ? h->ws_r[(it - 1) & 1].as<float>() : (const float*)nullptr, d_mag, coef, nb,
                       h->ws_A.as<float>(), h->K);
         }
     }
-    PK_TRY(synth_and_ola(h, L.sumF, d_tab + B, B, L.maxlen, d_out, "istft_gemm", "istft_ola"));
+    PK_TRY(synth_and_ola(h, L.sumF, d_tab + B, B, L.maxlen, d_out, fft ? "istft_fft" : "istft_gemm", "istft_ola"));
     if (flags & PK_HOST_IO) {
         if (L.sumS > 0) PK_HIP(hipMemcpyAsync(wav_out, d_out, (size_t)L.sumS * 4, hipMemcpyDeviceToHost, ctx->stream));
         PK_HIP(hipStreamSynchronize(ctx->stream));
     }
+    return PK_OK;
+}
+
+extern "C" int pk_istft_set_transform(pk_istft* h, int32_t transform) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_istft_set_transform: NULL argument");
+    if (transform != PK_TRANSFORM_DENSE && transform != PK_TRANSFORM_FFT)
+        PK_FAIL(PK_EINVAL, "pk_istft_set_transform: transform must be PK_TRANSFORM_DENSE (0) or PK_TRANSFORM_FFT (1), got %d",
+                (int)transform);
+    if (transform == PK_TRANSFORM_FFT) {
+        if (!pk_rfft_size_ok(h->cfg.n_fft))
+            PK_FAIL(PK_EUNSUPPORTED, "ISTFT: PK_TRANSFORM_FFT needs an n_fft that is " PK_RFFT_SIZES " (got %d); the dense "
+                    "transform takes any multiple of 16", (int)h->cfg.n_fft);
+        PK_DEVICE(h->ctx->device);
+        PK_TRY(pk_rfft_prepare(h->ctx, h->cfg.n_fft));
+    }
+    h->transform = transform;
     return PK_OK;
 }
 

@@ -9,12 +9,16 @@
 // = hop: row r (frame r) = xpad[r*hop .. r*hop + n_fft).  Utterances sit on one padded-sample axis
 // at hop-aligned offsets, so every frame of every utterance is one row of a single GEMM
 // (frames that straddle two utterances are computed and dropped by the row map).
+//
+// Under PK_TRANSFORM_FFT (pk_mel_set_transform) the same re | im rows come from the radix FFT of rfft.hip: it reads the same
+// padded-sample axis at stride hop, multiplies by the fp32 window and writes through the same row map.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "pk_gemm.h"
 #include "pk_mel.h"
+#include "pk_rfft.h"
 
 namespace {
 
@@ -101,7 +105,9 @@ struct pk_mel {
     pk_ctx* ctx = nullptr;
     pk_mel_cfg cfg;
     int n_bin = 0, ldspec = 0;
-    pk_dbuf d_dft, d_melw;          // packed GEMM weights
+    int transform = PK_TRANSFORM_DENSE;
+    std::vector<float> window;      // as given; d_window holds it once PK_TRANSFORM_FFT has been asked for
+    pk_dbuf d_dft, d_melw, d_window;   // packed GEMM weights
     pk_dbuf ws_tab, ws_ltab, ws_wav, ws_xpad, ws_reim, ws_spec, ws_out;
 };
 
@@ -119,6 +125,7 @@ extern "C" int pk_mel_create(pk_ctx* ctx, const pk_mel_cfg* cfg, const float* wi
     h->cfg = c;
     const int N = c.n_fft, nb = 1 + N / 2;
     h->n_bin = nb;
+    h->window.assign(window, window + N);
     h->ldspec = ((nb + PK_GEMM_BK - 1) / PK_GEMM_BK) * PK_GEMM_BK;
     // windowed DFT basis, np.fft.fft(np.eye(n_fft))[:n_bin] * window (:146-153): [K = n][N = re(k) | im(k)]
     {
@@ -148,6 +155,25 @@ extern "C" int pk_mel_create(pk_ctx* ctx, const pk_mel_cfg* cfg, const float* wi
 const pk_mel_cfg* pk_mel_config(const pk_mel* h) { return &h->cfg; }
 pk_ctx* pk_mel_context(const pk_mel* h) { return h->ctx; }
 const float* pk_mel_dft_packed(const pk_mel* h) { return h->d_dft.as<float>(); }
+int pk_mel_transform(const pk_mel* h) { return h->transform; }
+const float* pk_mel_window(const pk_mel* h) { return h->d_window.as<float>(); }
+
+extern "C" int pk_mel_set_transform(pk_mel* h, int32_t transform) {
+    if (!h) PK_FAIL(PK_EINVAL, "pk_mel_set_transform: NULL argument");
+    if (transform != PK_TRANSFORM_DENSE && transform != PK_TRANSFORM_FFT)
+        PK_FAIL(PK_EINVAL, "pk_mel_set_transform: transform must be PK_TRANSFORM_DENSE (0) or PK_TRANSFORM_FFT (1), got %d",
+                (int)transform);
+    if (transform == PK_TRANSFORM_FFT) {
+        if (!pk_rfft_size_ok(h->cfg.n_fft))
+            PK_FAIL(PK_EUNSUPPORTED, "STFT: PK_TRANSFORM_FFT needs an n_fft that is " PK_RFFT_SIZES " (got %d); the dense "
+                    "transform takes any multiple of 16", (int)h->cfg.n_fft);
+        PK_DEVICE(h->ctx->device);
+        PK_TRY(pk_rfft_prepare(h->ctx, h->cfg.n_fft));
+        if (!h->d_window.p) PK_TRY(pk_upload(h->ctx, h->d_window, h->window.data(), h->window.size() * sizeof(float)));
+    }
+    h->transform = transform;
+    return PK_OK;
+}
 
 extern "C" int pk_mel_num_frames(pk_mel* h, int32_t n_samples, int32_t* frames) {
     if (!h || !frames) PK_FAIL(PK_EINVAL, "pk_mel_num_frames: NULL argument");
@@ -217,7 +243,8 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
     PK_HIP(hipMemsetAsync(h->ws_xpad.p, 0, xpad_floats * 4, ctx->stream));
     PK_LAUNCH(ctx, "mel_reflect_pad", k_reflect_pad, dim3(pk_div_up(maxlen + 2 * pad, 256), B), dim3(256), 0, d_wav,
               d_tab, d_tab + B, h->ws_ltab.as<long>(), pad, h->ws_xpad.as<float>());
-    // STFT GEMM: [rows x n_fft] (lda = hop) x [n_fft x 2*n_bin]
+    // STFT GEMM: [rows x n_fft] (lda = hop) x [n_fft x 2*n_bin]; under PK_TRANSFORM_FFT the radix FFT writes the same rows
+    const bool fft = h->transform == PK_TRANSFORM_FFT;
     pk_gemm_args g;
     g.A = h->ws_xpad.as<float>();
     g.lda = hop;
@@ -231,12 +258,18 @@ extern "C" int pk_mel_run(pk_mel* h, const float* wav, const int32_t* lens, int3
         g.C = d_out;
         g.ldc = 2 * nb;
         g.out_rowmap = d_tab + 2 * B;
-        PK_TRY(pk_gemm_launch(ctx, "mel_stft_gemm", g));
+        if (fft)
+            PK_TRY(pk_rfft_forward(ctx, "mel_stft_fft", g.A, hop, h->d_window.as<float>(), g.out_rowmap, rows, N, g.C, g.ldc));
+        else
+            PK_TRY(pk_gemm_launch(ctx, "mel_stft_gemm", g));
     } else {
         PK_TRY(h->ws_reim.reserve((size_t)rows_alloc * 2 * nb * 4));
         g.C = h->ws_reim.as<float>();
         g.ldc = 2 * nb;
-        PK_TRY(pk_gemm_launch(ctx, "mel_stft_gemm", g));
+        if (fft)
+            PK_TRY(pk_rfft_forward(ctx, "mel_stft_fft", g.A, hop, h->d_window.as<float>(), nullptr, rows, N, g.C, g.ldc));
+        else
+            PK_TRY(pk_gemm_launch(ctx, "mel_stft_gemm", g));
         if (what == 3) {
             PK_LAUNCH(ctx, "mel_frame_energy", k_frame_energy, dim3(pk_div_up(rows, 4)), dim3(256), 0, h->ws_reim.as<float>(),
                       2 * nb, nb, rows, d_tab + 2 * B, c.log_floor, d_out);
@@ -312,7 +345,7 @@ extern "C" void pk_mel_destroy(pk_mel* h) {
     if (!h) return;
     pk_device_guard _dg(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    pk_dbuf* bufs[] = {&h->d_dft, &h->d_melw, &h->ws_tab, &h->ws_ltab, &h->ws_wav, &h->ws_xpad, &h->ws_reim,
+    pk_dbuf* bufs[] = {&h->d_dft, &h->d_melw, &h->d_window, &h->ws_tab, &h->ws_ltab, &h->ws_wav, &h->ws_xpad, &h->ws_reim,
                        &h->ws_spec, &h->ws_out};
     for (auto* b : bufs) b->release();
     delete h;

@@ -93,6 +93,9 @@ struct pk_ctx {
     // bound to: two engine handles issued concurrently on two streams of one context (Synthesizer.issue_acoustic) never
     // share a scratch buffer.
     std::map<hipStream_t, pk_ctx_scratch*> scratch;
+    // rfft.hip: the twiddle table of n = 2^(5 + i), uploaded when the context first needs that n (constant afterwards, so
+    // shared by every stream)
+    void* rfft_tw[8] = {};
 
     int prof_begin(const char* name);   // returns record index or -1
     void prof_end(int rec);

@@ -101,6 +101,8 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->edit_rev.release();
         delete kv.second;
     }
+    for (void* t : ctx->rfft_tw)
+        if (t) (void)hipFree(t);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -7,7 +7,11 @@ noise-plus-sines signals, the same initial phases on both sides.  Each figure is
 call, 5 warm-ups, >= 20 timed.  The dense-DFT formulation costs 2 * n_fft * (n_fft + 2) FLOP per frame and direction (an FFT
 is O(n log n)); the FLOP and byte counts below are computed from the shapes.
 
-  python tools/bench_griffin_lim.py [--utts 32] [--frames 640] [--iters 20] [--out FILE]
+``--transform fft`` runs the engine's calls on the radix FFT (csrc/rfft.hip) instead of the dense products; its lines carry
+no FLOP figure (the dense count does not apply) and the inverse moves no K-padded copy.  Run the two alternately in one
+session to compare them.
+
+  python tools/bench_griffin_lim.py [--utts 32] [--frames 640] [--iters 20] [--transform {dense,fft}] [--out FILE]
 """
 import argparse
 import json
@@ -59,14 +63,16 @@ def main():
     ap.add_argument("--hop", type=int, default=256)
     ap.add_argument("--n-iter", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--transform", choices=("dense", "fft"), default="dense")
     ap.add_argument("--out", default=None, help="append the lines to this file")
     args = ap.parse_args()
     from parakeet_amd import build as pk_build
     from parakeet_amd.audio import _Engine, _InvEngine
     N, hop, B, F = args.n_fft, args.hop, args.utts, args.frames
     nb = 1 + N // 2
-    fwd = _Engine(N, hop, N, "hann", True, False, None, 0)
-    inv = _InvEngine(N, hop, N, "hann", True)
+    fwd = _Engine(N, hop, N, "hann", True, False, None, 0, transform=args.transform)
+    inv = _InvEngine(N, hop, N, "hann", True, transform=args.transform)
+    dense = args.transform == "dense"
     rng = np.random.default_rng(3)
     t = np.arange(hop * (F - 1), dtype=np.float64)
     wavs = [(0.3 * np.sin(2 * np.pi * (0.01 + 0.001 * b) * t) + 0.05 * rng.standard_normal(t.size)).astype(np.float32)
@@ -75,7 +81,7 @@ def main():
     ph = torch.from_numpy(rng.random((B, F, nb)).astype(np.float32)).cuda() * (2 * np.pi)
     ang = [torch.cat([torch.cos(p), torch.sin(p)], 1).contiguous() for p in ph]
     spec = fwd.run(wavs, 0)
-    base = {"utts": B, "frames": F, "n_fft": N, "hop": hop, "n_iter": args.n_iter, "momentum": 0.99,
+    base = {"utts": B, "frames": F, "n_fft": N, "hop": hop, "n_iter": args.n_iter, "momentum": 0.99, "transform": args.transform,
             "device": torch.cuda.get_device_name(0), "host": os.uname().nodename, "source_hash": pk_build.source_hash()[:16]}
     rows = B * F
     flop_dir = 2.0 * N * (N + 2) * rows                                   # one dense transform of the batch
@@ -83,8 +89,8 @@ def main():
 
     ms, raw = timed(lambda: inv.griffin_lim(fwd, mags, args.n_iter, 0.99, None, ang), 5, args.iters)
     flop = flop_dir * (2 * args.n_iter + 1)
-    lines.append(dict(base, name="engine_griffin_lim", ms=round(ms, 3), raw_ms=raw, flop=flop,
-                      tflops=round(flop / ms * 1e-9, 2)))
+    lines.append(dict(base, name="engine_griffin_lim", ms=round(ms, 3), raw_ms=raw,
+                      **(dict(flop=flop, tflops=round(flop / ms * 1e-9, 2)) if dense else {})))
 
     win = torch.hann_window(N, periodic=True, device="cuda")
     S = torch.stack([m.transpose(0, 1) for m in mags])
@@ -95,10 +101,10 @@ def main():
     # one inverse of the batch; byte minimum: read spec, write and read the frame buffer, write wav
     ms, raw = timed(lambda: inv.run(spec), 5, args.iters)
     min_bytes = 4.0 * (rows * 2 * nb + 2 * rows * N + B * hop * (F - 1))
-    moved = min_bytes + 4.0 * 2 * rows * (N + 16)                         # + the K-padded copy of spec: written, read
-    lines.append(dict(base, name="engine_istft", ms=round(ms, 3), raw_ms=raw, flop=flop_dir,
-                      tflops=round(flop_dir / ms * 1e-9, 2), min_bytes=min_bytes, moved_bytes=moved,
-                      min_bytes_gbs=round(min_bytes / ms * 1e-6, 1)))
+    moved = min_bytes + (4.0 * 2 * rows * (N + 16) if dense else 0.0)    # + the K-padded copy of spec: written, read
+    lines.append(dict(base, name="engine_istft", ms=round(ms, 3), raw_ms=raw,
+                      **(dict(flop=flop_dir, tflops=round(flop_dir / ms * 1e-9, 2)) if dense else {}),
+                      min_bytes=min_bytes, moved_bytes=moved, min_bytes_gbs=round(min_bytes / ms * 1e-6, 1)))
     Xc = torch.stack([torch.complex(s[:, :nb], s[:, nb:]).transpose(0, 1) for s in spec])
     ms, raw = timed(lambda: torch.istft(Xc, N, hop_length=hop, win_length=N, window=win, center=True), 5, args.iters)
     lines.append(dict(base, name="torch_istft", ms=round(ms, 3), raw_ms=raw))
