@@ -11,8 +11,13 @@ With --discriminator-checkpoint (a snapshot_iter_*.pdz, which carries discrimina
 generated audio, eval/adversarial_loss and eval/fake_loss of it and eval/real_loss of the recording; their corpus means follow
 the two STFT lines.  Without it the output is what it always was.
 
+With --stoi every line gains two columns, the short-time objective intelligibility of the generated wav against the recording
+(STOI, Taal et al. 2011) and its extended form (ESTOI, Jensen & Taal 2016), on the pair as trimmed above and resampled to 10 kHz
+on the engine; the corpus means follow (over the pairs long enough to have a segment; shorter ones print nan).  The measure is
+this project's restatement of the papers, not pystoi's or MATLAB's code.
+
     python examples/score_vocoder.py --gen-dir generated --ref-dir recordings [--config conf/default.yaml]
-                                     [--discriminator-checkpoint snapshot_iter_400000.pdz]
+                                     [--discriminator-checkpoint snapshot_iter_400000.pdz] [--stoi]
 """
 import argparse
 import os
@@ -25,7 +30,7 @@ from parakeet_amd.audio import load_wav  # noqa: E402
 from parakeet_amd.stft_loss import MultiResolutionSTFTLoss  # noqa: E402
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gen-dir", required=True, help="generated waveforms")
     ap.add_argument("--ref-dir", required=True, help="recordings")
@@ -34,7 +39,8 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="pairs per call")
     ap.add_argument("--discriminator-checkpoint", default=None,
                     help="snapshot with discriminator_params: adds the discriminator's columns (needs --config)")
-    a = ap.parse_args()
+    ap.add_argument("--stoi", action="store_true", help="add STOI and ESTOI of generated against recording (at 10 kHz)")
+    a = ap.parse_args(argv)
     params, disc = {}, None
     if a.config:
         import yaml
@@ -51,9 +57,9 @@ def main():
     ids = sorted(f[:-4] for f in os.listdir(a.gen_dir) if f.endswith(".wav") and os.path.exists(os.path.join(a.ref_dir, f)))
     if not ids:
         raise SystemExit("no <utt_id>.wav present in both directories")
-    rows, drows = [], []
+    rows, drows, srows = [], [], []
     for i in range(0, len(ids), a.batch):
-        xs, ys, kept, notes = [], [], [], []
+        xs, ys, kept, notes, rates = [], [], [], [], []
         for u in ids[i:i + a.batch]:
             (x, sx), (y, sy) = load_wav(os.path.join(a.gen_dir, u + ".wav")), load_wav(os.path.join(a.ref_dir, u + ".wav"))
             rnote = ""
@@ -68,6 +74,7 @@ def main():
             xs.append(x[:n])
             ys.append(y[:n])
             kept.append(u)
+            rates.append(int(sy))
         if not kept:
             continue
         per = crit.per_utterance(xs, ys).mean(axis=1)            # (B, 2): mean over the resolutions
@@ -77,6 +84,17 @@ def main():
             d = np.stack([ml, sf[:, 0] / nf, sf[:, 1] / nf, sr[:, 0] / nr], 1)   # mean logit, adversarial, fake, real
             extra = ["".join(f"\t{v:.6f}" for v in row) for row in d]
             drows.extend(d)
+        if a.stoi:
+            from parakeet_amd.metrics import stoi_batch
+            by_rate = {}
+            for k, r in enumerate(rates):                            # one engine call per rate that occurs
+                by_rate.setdefault(r, []).append(k)
+            st = np.full((len(kept), 2), np.nan)
+            for r, ks in by_rate.items():
+                for c, ext in enumerate((False, True)):
+                    st[ks, c] = stoi_batch([ys[k] for k in ks], [xs[k] for k in ks], r, extended=ext)
+            extra = [e + f"\t{v[0]:.6f}\t{v[1]:.6f}" for e, v in zip(extra, st)]
+            srows.extend(st)
         for u, x, (sc, mag), e, note in zip(kept, xs, per, extra, notes):
             print(f"{u}\t{len(x)}\t{sc:.6f}\t{mag:.6f}{e}{note}")
             rows.append((sc, mag))
@@ -86,6 +104,13 @@ def main():
     if drows:
         ml, adv, fake, real = np.mean(drows, axis=0)
         print(f"mean_logit\t{ml:.6f}\nadversarial_loss\t{adv:.6f}\nfake_loss\t{fake:.6f}\nreal_loss\t{real:.6f}")
+    if srows:
+        ok = [r for r in srows if not np.isnan(r[0])]
+        if ok:
+            st, est = np.mean(ok, axis=0)
+            print(f"stoi\t{st:.6f}\nestoi\t{est:.6f}\tover {len(ok)} utterances")
+        else:
+            print("stoi\tnan\nestoi\tnan\tover 0 utterances")
 
 
 if __name__ == "__main__":

@@ -1197,6 +1197,45 @@ int pk_edit_run(pk_ctx* ctx, const int32_t* ref, const int32_t* hyp, const int64
  * 8, 16 with 64 R >= n (16 beyond), and keeps them in a global workspace when that is more. */
 int pk_edit_lds_words(int32_t* words);
 
+/* ------------------------------------- short-time objective intelligibility (STOI, ESTOI) */
+/* STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) of time-aligned pairs of signals at 10 kHz, ragged batches in one
+ * call (csrc/stoi.hip).  csrc/pk_stoi.h states the definition in full; it is this project's own restatement of
+ * the papers (NOT pystoi's or MATLAB's code), and fewer than 30 spectrum frames give NaN with segments = 0, not 1e-5.
+ * Signals, bands and outputs are DEVICE pointers unless said otherwise; offs is a HOST array of B + 1 ascending sample
+ * offsets, utterance b being the samples [offs[b], offs[b + 1]) of the packed signals (empty utterances are allowed).  No
+ * atomics, fixed summation orders: an utterance's results are the same bits alone, in any batch and at any position in it.
+ * Every call uploads its table (and synchronises for that), enqueues its kernels on the context's stream and reads nothing
+ * back.  Envelope (else PK_EUNSUPPORTED, nothing is launched): B <= 65535, 2^30 samples per utterance, 2^29 frames per call.
+ * PK_EINVAL: a NULL pointer that is needed, B <= 0, descending or negative offsets, a negative frame count. */
+typedef struct pk_stoi_result {
+    double d;           /* the score; NaN where segments == 0 */
+    int32_t segments;   /* S = (kept - 1) - 29, at least 0 */
+    int32_t kept;       /* frames of the clean signal that survive silent-frame removal */
+    int32_t frames;     /* F(L), the frames of the signal */
+    int32_t reserved;
+} pk_stoi_result;
+/* The whole pipeline: silent-frame removal decided on `clean`, both signals rebuilt, band magnitudes, segment correlations
+ * (extended != 0: ESTOI).  result_out: (B) records.  The kept-frame counts never reach the host. */
+int pk_stoi_run(pk_ctx* ctx, const float* clean, const float* degraded, const int64_t* offs, int32_t B, int32_t extended,
+                pk_stoi_result* result_out);
+/* Stage 1 alone.  With F_b = F(offs[b + 1] - offs[b]) and frames packed utterance after utterance (sum F_b entries):
+ *   energy_out  NULL, or float: e_i = 20 log10(||w x_i|| + EPS) in dB (the float64 value the test used, rounded);
+ *   keep_out    NULL, or uint8: 1 iff the frame is kept;
+ *   index_out   NULL, or int32: the first kept_out[b] entries of utterance b's stretch are its kept frames, ascending;
+ *   kept_out    (B) int32. */
+int pk_stoi_mask(pk_ctx* ctx, const float* clean, const int64_t* offs, int32_t B, float* energy_out, uint8_t* keep_out,
+                 int32_t* index_out, int32_t* kept_out);
+/* Stage 3 alone on given signals: every frame of x (F_b per utterance, nothing removed, nothing rebuilt) times w, zero-padded
+ * to 512, transformed on the radix FFT; bands_out: packed float (sum F_b, 15). */
+int pk_stoi_bands(pk_ctx* ctx, const float* x, const int64_t* offs, int32_t B, float* bands_out);
+/* Stage 4 alone: bands_x, bands_y packed float (sum frames[b], 15), frames HOST (B).  d_out (B) double, segments_out NULL or
+ * (B) int32: frames[b] - 29, at least 0. */
+int pk_stoi_segments(pk_ctx* ctx, const float* bands_x, const float* bands_y, const int32_t* frames, int32_t B,
+                     int32_t extended, double* d_out, int32_t* segments_out);
+/* HOST only: F(L) of the frame rule; the bins [lo[j], hi[j]) of the 15 one-third-octave bands. */
+int pk_stoi_num_frames(int64_t n_samples, int64_t* frames);
+int pk_stoi_band_edges(int32_t* lo, int32_t* hi);
+
 /* ------------------------------------------------------- feature statistics */
 /* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
  * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature

@@ -124,6 +124,11 @@ class PitchTrackCfg(C.Structure):
                 ("switch_cost", C.c_double)]
 
 
+class StoiResult(C.Structure):
+    """pk_stoi_result"""
+    _fields_ = [("d", C.c_double), ("segments", C.c_int32), ("kept", C.c_int32), ("frames", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("power", C.c_int32),
                 ("n_mels", C.c_int32), ("log_base", C.c_int32), ("log_floor", C.c_float)]
@@ -342,6 +347,12 @@ def _declare(lib):
         "pk_edit_run": (C.c_int, [vp, C.c_void_p, C.c_void_p, i64p, i64p, i32p, i32p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
         "pk_edit_lds_words": (C.c_int, [i32p]),
+        "pk_stoi_run": (C.c_int, [vp, f32p, f32p, i64p, i32, i32, C.c_void_p]),
+        "pk_stoi_mask": (C.c_int, [vp, f32p, i64p, i32, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pk_stoi_bands": (C.c_int, [vp, f32p, i64p, i32, f32p]),
+        "pk_stoi_segments": (C.c_int, [vp, f32p, f32p, i32p, i32, i32, C.c_void_p, C.c_void_p]),
+        "pk_stoi_num_frames": (C.c_int, [i64, i64p]),
+        "pk_stoi_band_edges": (C.c_int, [i32p, i32p]),
         "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "pk_stats_destroy": (None, [vp]),
         "pk_stats_reset": (C.c_int, [vp, f32p]),

@@ -162,6 +162,9 @@ struct pk_ctx_scratch {
     pk_dbuf edit_bits;   // passes, the reversed ops
     pk_dbuf edit_carry;
     pk_dbuf edit_rev;
+    pk_dbuf stoi_tab;    // stoi.hip: the call's table, the window (w | 256 zeros, uploaded once), the carved workspace of a call
+    pk_dbuf stoi_win;    // (pk_stoi.h: sized by the frame counts, the kept counts stay on the device)
+    pk_dbuf stoi_ws;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

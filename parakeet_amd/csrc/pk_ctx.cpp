@@ -99,6 +99,9 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->edit_bits.release();
         kv.second->edit_carry.release();
         kv.second->edit_rev.release();
+        kv.second->stoi_tab.release();
+        kv.second->stoi_win.release();
+        kv.second->stoi_ws.release();
         delete kv.second;
     }
     for (void* t : ctx->rfft_tw)
