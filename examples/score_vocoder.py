@@ -16,8 +16,14 @@ With --stoi every line gains two columns, the short-time objective intelligibili
 on the engine; the corpus means follow (over the pairs long enough to have a segment; shorter ones print nan).  The measure is
 this project's restatement of the papers, not pystoi's or MATLAB's code.
 
+With --loudness every line gains three columns, the gated programme loudness (ITU-R BS.1770-4, LUFS) of the generated wav and
+of the recording and their difference in LU, on the pair as trimmed above at the recording's rate; the corpus means follow (over
+the pairs where both are finite; a signal shorter than 400 ms or below -70 LUFS prints -inf).  The measure is this project's
+restatement of the Recommendation for mono, not pyloudnorm or libebur128; a pair at a rate that is no multiple
+of 10 Hz in 8 000 ... 192 000 prints nan.
+
     python examples/score_vocoder.py --gen-dir generated --ref-dir recordings [--config conf/default.yaml]
-                                     [--discriminator-checkpoint snapshot_iter_400000.pdz] [--stoi]
+                                     [--discriminator-checkpoint snapshot_iter_400000.pdz] [--stoi] [--loudness]
 """
 import argparse
 import os
@@ -40,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--discriminator-checkpoint", default=None,
                     help="snapshot with discriminator_params: adds the discriminator's columns (needs --config)")
     ap.add_argument("--stoi", action="store_true", help="add STOI and ESTOI of generated against recording (at 10 kHz)")
+    ap.add_argument("--loudness", action="store_true", help="add BS.1770 loudness (LUFS) of generated and recording, and the difference")
     a = ap.parse_args(argv)
     params, disc = {}, None
     if a.config:
@@ -57,7 +64,7 @@ def main(argv=None):
     ids = sorted(f[:-4] for f in os.listdir(a.gen_dir) if f.endswith(".wav") and os.path.exists(os.path.join(a.ref_dir, f)))
     if not ids:
         raise SystemExit("no <utt_id>.wav present in both directories")
-    rows, drows, srows = [], [], []
+    rows, drows, srows, lrows = [], [], [], []
     for i in range(0, len(ids), a.batch):
         xs, ys, kept, notes, rates = [], [], [], [], []
         for u in ids[i:i + a.batch]:
@@ -95,6 +102,21 @@ def main(argv=None):
                     st[ks, c] = stoi_batch([ys[k] for k in ks], [xs[k] for k in ks], r, extended=ext)
             extra = [e + f"\t{v[0]:.6f}\t{v[1]:.6f}" for e, v in zip(extra, st)]
             srows.extend(st)
+        if a.loudness:
+            from parakeet_amd.metrics import loudness_batch
+            by_rate = {}
+            for k, r in enumerate(rates):                            # one engine call per rate that occurs
+                by_rate.setdefault(r, []).append(k)
+            lu = np.full((len(kept), 2), np.nan)
+            for r, ks in by_rate.items():
+                try:
+                    lu[ks, 0], lu[ks, 1] = loudness_batch([xs[k] for k in ks], r), loudness_batch([ys[k] for k in ks], r)
+                except NotImplementedError:                          # a rate off the 100 ms sample grid: nan
+                    pass
+            with np.errstate(invalid="ignore"):
+                lu = np.concatenate([lu, lu[:, :1] - lu[:, 1:]], axis=1)
+            extra = [e + f"\t{v[0]:.3f}\t{v[1]:.3f}\t{v[2]:.3f}" for e, v in zip(extra, lu)]
+            lrows.extend(lu)
         for u, x, (sc, mag), e, note in zip(kept, xs, per, extra, notes):
             print(f"{u}\t{len(x)}\t{sc:.6f}\t{mag:.6f}{e}{note}")
             rows.append((sc, mag))
@@ -111,6 +133,13 @@ def main(argv=None):
             print(f"stoi\t{st:.6f}\nestoi\t{est:.6f}\tover {len(ok)} utterances")
         else:
             print("stoi\tnan\nestoi\tnan\tover 0 utterances")
+    if lrows:
+        ok = [r for r in lrows if np.isfinite(r).all()]
+        if ok:
+            g, r, d = np.mean(ok, axis=0)
+            print(f"loudness_generated\t{g:.3f}\nloudness_recording\t{r:.3f}\nloudness_difference\t{d:.3f}\tover {len(ok)} utterances")
+        else:
+            print("loudness_generated\tnan\nloudness_recording\tnan\nloudness_difference\tnan\tover 0 utterances")
 
 
 if __name__ == "__main__":

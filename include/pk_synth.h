@@ -1236,6 +1236,35 @@ int pk_stoi_segments(pk_ctx* ctx, const float* bands_x, const float* bands_y, co
 int pk_stoi_num_frames(int64_t n_samples, int64_t* frames);
 int pk_stoi_band_edges(int32_t* lo, int32_t* hi);
 
+/* ------------------------------------- recursive filters, gated loudness (BS.1770, mono), gain */
+/* Cascades of second-order sections over ragged batches in float64, and programme loudness on the same passes (csrc/iir.hip,
+ * DESIGN 4.5h).  csrc/pk_iir.h states the recurrence, the plan of 256-sample chunks and every summation order; the loudness
+ * measure is this project's own restatement of ITU-R BS.1770-4 for one channel (NOT pyloudnorm, NOT libebur128), with blocks
+ * on a 100 ms sample grid.  x, y and the result arrays are DEVICE pointers; lens and gains are HOST arrays of B entries,
+ * utterance b being lens[b] samples of the packed signal behind utterance b - 1 (empty utterances are allowed and produce
+ * nothing).  No atomics, fixed orders: an utterance's results are the same bits alone, in any batch and at any position.
+ * Every call uploads its table (and synchronises for that), enqueues its kernels on the context's stream and reads nothing
+ * back.  Envelope (else PK_EUNSUPPORTED, nothing is launched): B <= 65535, 2^30 samples per utterance, at most 8 sections,
+ * sr a multiple of 10 in 8 000 ... 192 000.  PK_EINVAL: a NULL pointer, B <= 0, a negative length, fewer than one section,
+ * a0 != 1, a coefficient that is not finite. */
+typedef struct pk_iir pk_iir;
+/* sos: HOST (n_sections, 6) double, scipy's rows (b0, b1, b2, a0, a1, a2) with a0 == 1.  The transition matrix of a chunk is
+ * computed on the device here, once. */
+int pk_iir_create(pk_ctx* ctx, const double* sos, int32_t n_sections, pk_iir** out);
+void pk_iir_destroy(pk_iir* h);
+/* The transition matrix P, (2 n_sections, 2 n_sections) row-major, into a HOST array. */
+int pk_iir_transition(pk_iir* h, double* P_out);
+/* y = the filter of x, the state zero at every utterance's first sample; one float32 rounding per sample. */
+int pk_iir_run(pk_iir* h, const float* x, const int32_t* lens, int32_t B, float* y);
+/* Gated loudness of x at rate sr, h holding the weighting filter (K-weighting for BS.1770).  Per utterance: mean_out (B)
+ * double, the mean power of the blocks both gates keep (0 where none); rel_out (B) double, the relative threshold as a power
+ * (0 where the absolute gate keeps nothing); peak_out (B) float, max|x|; counts_out (B, 3) int32: the blocks both gates keep,
+ * those the absolute gate keeps, all blocks.  LUFS = -0.691 + 10 log10(mean) is the host's to form. */
+int pk_loudness_run(pk_iir* h, const float* x, const int32_t* lens, int32_t B, int32_t sr, double* mean_out, double* rel_out,
+                    float* peak_out, int32_t* counts_out);
+/* y = x * gains[b] over utterance b, one rounding (y may be x). */
+int pk_gain_run(pk_ctx* ctx, const float* x, const int32_t* lens, int32_t B, const float* gains, float* y);
+
 /* ------------------------------------------------------- feature statistics */
 /* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
  * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature

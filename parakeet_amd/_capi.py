@@ -353,6 +353,12 @@ def _declare(lib):
         "pk_stoi_segments": (C.c_int, [vp, f32p, f32p, i32p, i32, i32, C.c_void_p, C.c_void_p]),
         "pk_stoi_num_frames": (C.c_int, [i64, i64p]),
         "pk_stoi_band_edges": (C.c_int, [i32p, i32p]),
+        "pk_iir_create": (C.c_int, [vp, C.POINTER(C.c_double), i32, C.POINTER(vp)]),
+        "pk_iir_destroy": (None, [vp]),
+        "pk_iir_transition": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "pk_iir_run": (C.c_int, [vp, f32p, i32p, i32, f32p]),
+        "pk_loudness_run": (C.c_int, [vp, f32p, i32p, i32, i32, C.c_void_p, C.c_void_p, f32p, C.c_void_p]),
+        "pk_gain_run": (C.c_int, [vp, f32p, i32p, i32, C.POINTER(C.c_float), f32p]),
         "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "pk_stats_destroy": (None, [vp]),
         "pk_stats_reset": (C.c_int, [vp, f32p]),

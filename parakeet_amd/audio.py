@@ -22,6 +22,10 @@ whose resampler is not available here and is not reproduced), run by csrc/resamp
 ``Pitch`` / ``pitch_lags`` / ``continuous_f0_batch``: the reference's ``Pitch`` interface (get_feats.py:91-164) over this
 project's own f0 estimator (csrc/pitch.hip; NOT pyworld's DIO + StoneMask) and the reference's continuous-f0,
 log and token-average steps.
+
+``sosfilt`` / ``lfilter`` / ``preemphasis`` / ``deemphasis``: recursive filters as cascades of second-order sections in float64
+(csrc/iir.hip), ``k_weighting`` and ``normalize_loudness``: gated programme loudness after ITU-R BS.1770-4 as
+this project restates it for mono (NOT pyloudnorm, NOT libebur128; blocks on a 100 ms sample grid, ``sr % 10 == 0``).
 """
 import ctypes as C
 import math
@@ -849,6 +853,227 @@ def peak_normalize_batch(wavs, device=None):
 
 def peak_normalize(y, device=None):
     return peak_normalize_batch([y], device)[0]
+
+
+# ---------------------------------------------------------------------- recursive filters and loudness
+# csrc/pk_iir.h: cascades of biquads in float64, cut into chunks of 256 samples and stitched by a carry over the chunks; the
+# same bits for an utterance alone, in any batch and at any position.  The engine's envelope:
+IIR_MAX_SECTIONS, IIR_CHUNK = 8, 256
+LOUDNESS_SR_MIN, LOUDNESS_SR_MAX = 8000, 192000
+_IIR_HANDLES = {}
+
+
+class _IIREngine:
+    """One ``pk_iir`` handle: the sections and their chunk transition matrix on one device."""
+
+    def __init__(self, sos, device=None):
+        self.ctx = Context.get(device)
+        self.sos = sos
+        h = C.c_void_p()
+        _capi.check(self.ctx.lib.pk_iir_create(self.ctx.handle, sos.ctypes.data_as(C.POINTER(C.c_double)), int(sos.shape[0]),
+                                               C.byref(h)))
+        self.h = h
+
+    def transition(self):
+        """The (2 S, 2 S) float64 transition matrix of one chunk, as the device computed it."""
+        n = 2 * int(self.sos.shape[0])
+        P = np.empty((n, n), dtype=np.float64)
+        _capi.check(self.ctx.lib.pk_iir_transition(self.h, P.ctypes.data_as(C.POINTER(C.c_double))))
+        return P
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.ctx.lib.pk_iir_destroy(h)
+            except Exception:
+                pass
+
+
+def _check_sos(sos):
+    """scipy's (S, 6) rows as a contiguous float64 array; the refusals of ``pk_iir_create``, raised before a device is needed."""
+    sos = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    if sos.ndim != 2 or sos.shape[1] != 6 or sos.shape[0] < 1:
+        raise ValueError(f"sos must have shape (n_sections >= 1, 6), got {sos.shape}")
+    if sos.shape[0] > IIR_MAX_SECTIONS:
+        raise NotImplementedError(f"{sos.shape[0]} sections; the engine's limit is {IIR_MAX_SECTIONS}")
+    if not np.isfinite(sos).all():
+        raise ValueError("sos has a coefficient that is not finite")
+    if (sos[:, 3] != 1.0).any():
+        raise ValueError("every section must be normalised to a0 = 1 (as scipy.signal.sosfilt requires)")
+    return sos
+
+
+def _iir_engine(sos, device=None):
+    sos = _check_sos(sos)
+    ctx = Context.get(device)
+    key = (str(ctx.device), sos.tobytes())
+    if key not in _IIR_HANDLES:
+        _IIR_HANDLES[key] = _IIREngine(sos, device)
+    return _IIR_HANDLES[key]
+
+
+def _pack_ragged(ctx, wavs, what):
+    """A list of 1-D signals, empty ones allowed -> (lens int32, the packed float32 device buffer)."""
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError(f"{what}: no signal given")
+    for b, w in enumerate(wavs):
+        if not hasattr(w, "shape") or len(w.shape) != 1:
+            raise ValueError(f"{what}: signal {b} is not 1-D" + (f" (shape {tuple(w.shape)})" if hasattr(w, "shape") else ""))
+    xs = [ctx.to_device(w).reshape(-1) for w in wavs]
+    lens = np.array([x.numel() for x in xs], dtype=np.int32)
+    x = xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+    if x.numel() == 0:
+        x = ctx.empty((1,))                                 # a pointer to pass; nothing of it is read
+    return lens, x
+
+
+def sosfilt_batch(sos, wavs, device=None):
+    """``scipy.signal.sosfilt(sos, x)`` for a ragged list of float32 signals in one engine call: float64 inside, zero initial
+    state, one float32 rounding per sample.  A list of device tensors.  At most 8 sections (``NotImplementedError`` beyond)."""
+    eng = _iir_engine(sos, device)
+    ctx = eng.ctx
+    lens, x = _pack_ragged(ctx, wavs, "sosfilt")
+    out = ctx.empty((max(int(lens.sum()), 1),))
+    _capi.check(ctx.lib.pk_iir_run(eng.h, dptr(x), _i32p(lens), len(lens), dptr(out)))
+    return [wrap(o) for o in torch.split(out[:int(lens.sum())], [int(n) for n in lens])]
+
+
+def sosfilt(sos, x, device=None):
+    return sosfilt_batch(sos, [x], device)[0]
+
+
+def _lfilter_sos(b, a):
+    b, a = [float(v) for v in np.asarray(b, dtype=np.float64).reshape(-1)], [float(v) for v in np.asarray(a, dtype=np.float64).reshape(-1)]
+    if not b or not a:
+        raise ValueError("lfilter: b and a need at least one coefficient each")
+    if len(b) > 3 or len(a) > 3:
+        raise NotImplementedError(f"lfilter takes up to three coefficients each (got {len(b)} and {len(a)}); factor a longer "
+                                  "filter into second-order sections (scipy.signal.tf2sos) and call sosfilt")
+    if a[0] == 0.0 or not all(math.isfinite(v) for v in b + a):
+        raise ValueError("lfilter: a[0] must not be 0 and every coefficient must be finite")
+    b, a = b + [0.0] * (3 - len(b)), a + [0.0] * (3 - len(a))
+    return np.array([[b[0] / a[0], b[1] / a[0], b[2] / a[0], 1.0, a[1] / a[0], a[2] / a[0]]], dtype=np.float64)
+
+
+def lfilter(b, a, x, device=None):
+    """``scipy.signal.lfilter`` for ``len(b), len(a) <= 3``: one section, normalised by a[0] on the host."""
+    return sosfilt(_lfilter_sos(b, a), x, device)
+
+
+def lfilter_batch(b, a, wavs, device=None):
+    return sosfilt_batch(_lfilter_sos(b, a), wavs, device)
+
+
+def _check_coef(coef):
+    coef = float(coef)
+    if not math.isfinite(coef):
+        raise ValueError(f"coef = {coef} must be finite")
+    return coef
+
+
+def preemphasis_batch(wavs, coef=0.97, device=None):
+    """y[n] = x[n] - coef x[n - 1] (``librosa.effects.preemphasis`` with a zero initial state)."""
+    return sosfilt_batch([[1.0, -_check_coef(coef), 0.0, 1.0, 0.0, 0.0]], wavs, device)
+
+
+def preemphasis(x, coef=0.97, device=None):
+    return preemphasis_batch([x], coef, device)[0]
+
+
+def deemphasis_batch(wavs, coef=0.97, device=None):
+    """y[n] = x[n] + coef y[n - 1], the inverse of ``preemphasis``."""
+    return sosfilt_batch([[1.0, 0.0, 0.0, 1.0, -_check_coef(coef), 0.0]], wavs, device)
+
+
+def deemphasis(x, coef=0.97, device=None):
+    return deemphasis_batch([x], coef, device)[0]
+
+
+def _check_loudness_sr(sr):
+    if int(sr) != sr or sr < 1:
+        raise ValueError(f"sr = {sr} must be a positive integer")
+    sr = int(sr)
+    if sr % 10 != 0 or not LOUDNESS_SR_MIN <= sr <= LOUDNESS_SR_MAX:
+        raise NotImplementedError(f"sr = {sr}: loudness blocks lie on a 100 ms sample grid, which takes a multiple of 10 Hz in "
+                                  f"{LOUDNESS_SR_MIN} ... {LOUDNESS_SR_MAX}; resample first")
+    return sr
+
+
+def k_weighting(sr):
+    """The K-weighting of ITU-R BS.1770 at rate ``sr`` as a (2, 6) float64 sos array (the shelf, then the high-pass), by the
+    formulas libebur128 uses; at 48 000 Hz they reproduce the Recommendation's table.  Host arithmetic in Python floats."""
+    sr = _check_loudness_sr(sr)
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    hp = [1.0, -2.0, 1.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    return np.array([shelf, hp], dtype=np.float64)
+
+
+def _loudness_run(wavs, sr, device=None):
+    """One engine call -> (ctx, lens, the packed signal, dict of host arrays per utterance: ``mean_power``, ``rel`` (float64),
+    ``peak`` (float32), ``gated``, ``gated_abs``, ``blocks`` (int32), ``lufs`` (float64, -inf where no block is kept))."""
+    sr = _check_loudness_sr(sr)
+    eng = _iir_engine(k_weighting(sr), device)
+    ctx = eng.ctx
+    lens, x = _pack_ragged(ctx, wavs, "loudness")
+    B = len(lens)
+    mean, rel = ctx.empty((B,), torch.float64), ctx.empty((B,), torch.float64)
+    peak, counts = ctx.empty((B,)), ctx.empty((B * 3,), torch.int32)
+    _capi.check(ctx.lib.pk_loudness_run(eng.h, dptr(x), _i32p(lens), B, sr, dptr(mean), dptr(rel), dptr(peak), dptr(counts)))
+    host = torch.cat([t.view(torch.uint8) for t in (mean, rel, peak, counts)]).cpu().numpy()     # the one read
+    mean_h, rel_h = host[:8 * B].view(np.float64), host[8 * B:16 * B].view(np.float64)
+    peak_h, cnt_h = host[16 * B:20 * B].view(np.float32), host[20 * B:].view(np.int32).reshape(B, 3)
+    with np.errstate(divide="ignore"):
+        lufs = np.where(cnt_h[:, 0] > 0, -0.691 + 10.0 * np.log10(np.where(cnt_h[:, 0] > 0, mean_h, 1.0)), -np.inf)
+    return ctx, lens, x, dict(mean_power=mean_h.copy(), rel=rel_h.copy(), peak=peak_h.copy(), gated=cnt_h[:, 0].copy(),
+                              gated_abs=cnt_h[:, 1].copy(), blocks=cnt_h[:, 2].copy(), lufs=lufs)
+
+
+def normalize_loudness_batch(wavs, sr, target_lufs=-23.0, max_peak=None, return_gains=False, device=None):
+    """Every utterance scaled to ``target_lufs`` of gated BS.1770 loudness (``metrics.loudness_batch``; this project's own
+    restatement for mono, blocks on a 100 ms sample grid): g = 10^((target - LUFS) / 20) in float64 on the host, capped at
+    ``max_peak / peak`` when ``max_peak`` is given (and then stepped down in float32 until the rounded peak sample does not
+    exceed it), rounded to float32 and applied on the engine with one rounding per sample.  An utterance whose loudness is
+    -inf (shorter than 400 ms, or nothing above -70 LUFS) comes back unchanged with gain 1.  A list of device tensors;
+    ``return_gains``: also the float32 gains."""
+    target = float(target_lufs)
+    if not math.isfinite(target):
+        raise ValueError(f"target_lufs = {target_lufs} must be finite")
+    if max_peak is not None and not (math.isfinite(float(max_peak)) and float(max_peak) > 0.0):
+        raise ValueError(f"max_peak = {max_peak} must be a positive finite number")
+    ctx, lens, x, m = _loudness_run(wavs, sr, device)
+    gains = np.ones(len(lens), dtype=np.float32)
+    for b, (lufs, peak) in enumerate(zip(m["lufs"], m["peak"])):
+        if not math.isfinite(lufs):
+            continue
+        g = 10.0 ** ((target - float(lufs)) / 20.0)
+        if max_peak is not None and peak > 0:
+            g = min(g, float(max_peak) / float(peak))
+        g32 = np.float32(g)
+        if max_peak is not None:
+            while g32 > 0 and float(np.float32(peak) * g32) > float(max_peak):      # the device's product, rounded the same way
+                g32 = np.nextafter(g32, np.float32(0))
+        gains[b] = g32
+    out = ctx.empty((max(int(lens.sum()), 1),))
+    _capi.check(ctx.lib.pk_gain_run(ctx.handle, dptr(x), _i32p(lens), len(lens), gains.ctypes.data_as(C.POINTER(C.c_float)),
+                                    dptr(out)))
+    res = [wrap(o) for o in torch.split(out[:int(lens.sum())], [int(n) for n in lens])]
+    return (res, gains) if return_gains else res
+
+
+def normalize_loudness(y, sr, target_lufs=-23.0, max_peak=None, return_gains=False, device=None):
+    out = normalize_loudness_batch([y], sr, target_lufs, max_peak, return_gains, device)
+    return (out[0][0], out[1][0]) if return_gains else out[0]
 
 
 def _check_vad_envelope(window, width, silence):

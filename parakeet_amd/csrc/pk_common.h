@@ -165,6 +165,8 @@ struct pk_ctx_scratch {
     pk_dbuf stoi_tab;    // stoi.hip: the call's table, the window (w | 256 zeros, uploaded once), the carved workspace of a call
     pk_dbuf stoi_win;    // (pk_stoi.h: sized by the frame counts, the kept counts stay on the device)
     pk_dbuf stoi_ws;
+    pk_dbuf iir_tab;     // iir.hip: the call's table; the chunk states, loudness pieces, peaks and hop segments of a call (pk_iir.h)
+    pk_dbuf iir_ws;
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

@@ -102,6 +102,8 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->stoi_tab.release();
         kv.second->stoi_win.release();
         kv.second->stoi_ws.release();
+        kv.second->iir_tab.release();
+        kv.second->iir_ws.release();
         delete kv.second;
     }
     for (void* t : ctx->rfft_tw)
