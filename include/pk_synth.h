@@ -1265,6 +1265,20 @@ int pk_loudness_run(pk_iir* h, const float* x, const int32_t* lens, int32_t B, i
 /* y = x * gains[b] over utterance b, one rounding (y may be x). */
 int pk_gain_run(pk_ctx* ctx, const float* x, const int32_t* lens, int32_t B, const float* gains, float* y);
 
+/* ------------------------------------------------------- phase vocoder (time stretching, pitch shifting) */
+/* A spectrogram re-timed by a rate (csrc/pvoc.hip): what librosa 0.8's phase_vocoder(D, rate, hop_length)
+ * computes, as this project restates it in float64 without any transcendental function (csrc/pk_pvoc.h states every
+ * operation; the accumulated phase is a running product of unit phasors, hop_length has no effect).  NOT librosa's bits, no
+ * phase locking.  spec and out are DEVICE pointers to packed ragged rows of 2 * n_bin floats, re | im, the layout of
+ * pk_mel_run(what = 0) and pk_istft_run: utterance b is frames[b] rows of spec behind utterance b - 1, and T_b rows of out,
+ * T_b = ceil(frames[b] / rates[b]) in float64 (pk_pvoc_num_frames).  frames and rates are HOST arrays of B entries, one rate
+ * per utterance.  No atomics, no reduction: an utterance's bytes are the same alone, in any batch and at any position.  The
+ * call uploads its table (and synchronises for that), enqueues one kernel on the context's stream and reads nothing back.
+ * PK_EINVAL: a NULL pointer, B <= 0, n_bin < 1, a frame count below 1, a rate that is not finite or not > 0, T_b >= 2^31.
+ * PK_EUNSUPPORTED: B > 65535. */
+int pk_pvoc_num_frames(int64_t frames, double rate, int64_t* out_frames);
+int pk_pvoc_run(pk_ctx* ctx, const float* spec, const int32_t* frames, int32_t B, int32_t n_bin, const double* rates, float* out);
+
 /* ------------------------------------------------------- feature statistics */
 /* Streaming mean / variance of ragged feature matrices (csrc/stats.hip): what the reference's
  * utils/compute_statistics.py takes from scikit-learn's StandardScaler.partial_fit.  A handle is an accumulator over feature

@@ -359,6 +359,8 @@ def _declare(lib):
         "pk_iir_run": (C.c_int, [vp, f32p, i32p, i32, f32p]),
         "pk_loudness_run": (C.c_int, [vp, f32p, i32p, i32, i32, C.c_void_p, C.c_void_p, f32p, C.c_void_p]),
         "pk_gain_run": (C.c_int, [vp, f32p, i32p, i32, C.POINTER(C.c_float), f32p]),
+        "pk_pvoc_num_frames": (C.c_int, [i64, C.c_double, i64p]),
+        "pk_pvoc_run": (C.c_int, [vp, f32p, i32p, i32, i32, C.POINTER(C.c_double), f32p]),
         "pk_stats_create": (C.c_int, [vp, i32, C.POINTER(vp)]),
         "pk_stats_destroy": (None, [vp]),
         "pk_stats_reset": (C.c_int, [vp, f32p]),

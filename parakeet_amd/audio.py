@@ -26,6 +26,10 @@ log and token-average steps.
 ``sosfilt`` / ``lfilter`` / ``preemphasis`` / ``deemphasis``: recursive filters as cascades of second-order sections in float64
 (csrc/iir.hip), ``k_weighting`` and ``normalize_loudness``: gated programme loudness after ITU-R BS.1770-4 as
 this project restates it for mono (NOT pyloudnorm, NOT libebur128; blocks on a 100 ms sample grid, ``sr % 10 == 0``).
+
+``phase_vocoder`` / ``time_stretch`` / ``pitch_shift`` (and their ``_batch`` forms): the two effects of ``librosa.effects`` the
+set lacked, over librosa 0.8's phase vocoder as this project restates it without any transcendental function (DESIGN.md 4.5i,
+csrc/pvoc.hip; no phase locking; ``pitch_shift`` resamples with this project's filter at a rational ratio).
 """
 import ctypes as C
 import math
@@ -1328,6 +1332,209 @@ def resample(y, orig_sr, target_sr, **kw):
     rows = y.reshape(-1, y.shape[-1])
     out = rs.run_batch(list(rows))
     return torch.stack(out).cpu().numpy().reshape(y.shape[:-1] + (-1,))
+
+
+# ---------------------------------------------------------------------- time stretching and pitch shifting
+# csrc/pk_pvoc.h: librosa 0.8's ``phase_vocoder`` restated in float64 without any transcendental function (the accumulated
+# phase is a running product of unit phasors), one lane per (utterance, bin); the same bits for an utterance alone, in any
+# batch and at any position.  No phase locking: the usual phasiness and the amplitude loss on stretched tones remain.
+PVOC_MAX_FRAMES = 1 << 31
+PITCH_SHIFT_MAX_DENOMINATOR = 1000
+_STRETCH_ENGINES = {}
+
+
+def _check_rate(rate, what):
+    try:
+        r = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: rate = {rate!r} is not a number") from None
+    if not math.isfinite(r) or not r > 0.0:
+        raise ValueError(f"{what}: rate = {r} must be finite and > 0")
+    return r
+
+
+def _check_rates(rates, n, what):
+    rates = [rates] * n if np.ndim(rates) == 0 else list(rates)
+    if len(rates) != n:
+        raise ValueError(f"{what}: {len(rates)} rates for {n} utterances; one rate per utterance is needed")
+    return [_check_rate(r, what) for r in rates]
+
+
+def _check_signals(wavs, what):
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError(f"{what}: no signal given")
+    for b, w in enumerate(wavs):
+        if not hasattr(w, "shape") or len(w.shape) != 1:
+            raise ValueError(f"{what}: signal {b} is not 1-D" + (f" (shape {tuple(w.shape)})" if hasattr(w, "shape") else ""))
+        if int(w.shape[0]) < 1:
+            raise ValueError(f"{what}: signal {b} is empty")
+    return wavs
+
+
+def pvoc_num_frames(frames, rate):
+    """T = ceil(frames / rate) in float64 = ``len(numpy.arange(0, frames, rate))``, from the engine's own function (host only);
+    ``ValueError`` for frames < 1, a rate that is not finite or not > 0, T >= 2^31."""
+    t = C.c_int64()
+    _capi.check(_capi.lib().pk_pvoc_num_frames(int(frames), float(rate), C.byref(t)))
+    return t.value
+
+
+def _pvoc_packed(ctx, x, frames, rates, n_bin):
+    """x: the packed (sum(frames), 2 * n_bin) device rows -> (the packed output rows, [T_b]); one engine call."""
+    nt = [pvoc_num_frames(f, r) for f, r in zip(frames, rates)]
+    out = ctx.empty((sum(nt), 2 * n_bin))
+    fr, rt = np.asarray(frames, dtype=np.int32), np.asarray(rates, dtype=np.float64)
+    _capi.check(ctx.lib.pk_pvoc_run(ctx.handle, dptr(x), _i32p(fr), len(fr), int(n_bin), rt.ctypes.data_as(C.POINTER(C.c_double)),
+                                    dptr(out)))
+    return out, nt
+
+
+def phase_vocoder_batch(specs, rates, device=None):
+    """Re-time spectrograms: a ragged list of (frames_b, 2 * n_bin) re | im rows (``pk_mel_run`` what = 0, what
+    ``ISTFT.inverse_batch`` takes) and one rate per utterance (or one number for all) -> a list of (T_b, 2 * n_bin) device
+    tensors, T_b = ``pvoc_num_frames(frames_b, rate_b)``, in one engine call.  rate > 1 shortens, rate < 1 lengthens."""
+    specs = list(specs)
+    if not specs:
+        raise ValueError("phase_vocoder: no spectrogram given")
+    for b, s in enumerate(specs):
+        if not hasattr(s, "shape") or len(s.shape) != 2 or s.shape[1] < 2 or s.shape[1] % 2 or s.shape[0] < 1:
+            raise ValueError(f"phase_vocoder: spectrogram {b} is not (frames >= 1, 2 * n_bin) re | im rows"
+                             + (f" (shape {tuple(s.shape)})" if hasattr(s, "shape") else ""))
+        if s.shape[1] != specs[0].shape[1]:
+            raise ValueError(f"phase_vocoder: spectrogram {b} has {s.shape[1]} columns, spectrogram 0 has {specs[0].shape[1]}")
+    rates = _check_rates(rates, len(specs), "phase_vocoder")
+    frames = [int(s.shape[0]) for s in specs]
+    for f, r in zip(frames, rates):
+        pvoc_num_frames(f, r)                               # T >= 2^31 is refused before a device is needed
+    ctx = Context.get(device)
+    xs = [ctx.to_device(s) for s in specs]
+    out, nt = _pvoc_packed(ctx, xs[0] if len(xs) == 1 else torch.cat(xs), frames, rates, specs[0].shape[1] // 2)
+    return [wrap(o) for o in torch.split(out, nt)]
+
+
+def phase_vocoder(D, rate, hop_length=None, device=None):
+    """``librosa.phase_vocoder(D, rate, hop_length)``'s shape: complex (n_bin, frames) -> complex64 (n_bin, T), a numpy array
+    for a numpy array and a device tensor for a tensor.  ``hop_length`` is accepted and HAS NO EFFECT: modulo 2 pi the expected
+    phase advance it enters is subtracted and added back."""
+    del hop_length
+    is_t = isinstance(D, torch.Tensor)
+    if not hasattr(D, "shape") or len(D.shape) != 2 or D.shape[0] < 1 or D.shape[1] < 1 or not (
+            D.is_complex() if is_t else np.iscomplexobj(D)):
+        raise ValueError("phase_vocoder: expected a complex (n_bin, frames) spectrogram"
+                         + (f", got shape {tuple(D.shape)}" if hasattr(D, "shape") else ""))
+    rate = _check_rate(rate, "phase_vocoder")
+    if is_t:
+        D = D.as_subclass(torch.Tensor)
+        rows = torch.cat([D.real, D.imag], 0).transpose(0, 1).to(torch.float32)
+    else:
+        rows = np.ascontiguousarray(np.concatenate([D.real.T, D.imag.T], axis=1), dtype=np.float32)
+    out = phase_vocoder_batch([rows], [rate], device)[0].as_subclass(torch.Tensor)
+    nb = D.shape[0]
+    res = torch.complex(out[:, :nb], out[:, nb:]).transpose(0, 1)
+    return wrap(res.contiguous()) if is_t else res.cpu().numpy()
+
+
+def _stretch_engines(n_fft, hop_length, win_length, window, transform, device=None):
+    """The forward and the inverse STFT handle of one configuration (center=True, reflect padding), created once."""
+    ctx = Context.get(device)
+    key = (int(n_fft), int(hop_length), int(win_length), window, transform, str(ctx.device))
+    if key not in _STRETCH_ENGINES:
+        _STRETCH_ENGINES[key] = (_Engine(n_fft, hop_length, win_length, window, True, False, None, 0, device, transform),
+                                 _InvEngine(n_fft, hop_length, win_length, window, True, device, transform))
+    return _STRETCH_ENGINES[key]
+
+
+def stretched_length(n, rate):
+    """``int(round(n / rate))``, librosa's ``len_stretch``.  Python's ``round`` takes a tie to the EVEN integer (2.5 -> 2,
+    3.5 -> 4), and so does this."""
+    return int(round(int(n) / float(rate)))
+
+
+def _fit_length(y, n):
+    """Crop or zero-pad a 1-D device tensor to n samples (librosa's ``fix_length``)."""
+    if y.numel() >= n:
+        return y[:n]
+    return torch.cat([y, torch.zeros(n - y.numel(), dtype=y.dtype, device=y.device)])
+
+
+def time_stretch_batch(wavs, rates, n_fft=2048, hop_length=None, win_length=None, window="hann", transform="dense", device=None):
+    """``librosa.effects.time_stretch`` for a ragged list of float32 signals, one rate per utterance (or one number for all):
+    STFT (center=True, reflect padding) -> phase vocoder -> ISTFT as three engine calls with nothing read back in between; frame
+    counts and lengths follow from the input lengths on the host.  Each result is cropped or zero-padded to
+    ``stretched_length(len(y), rate)`` samples.  ``hop_length`` defaults to ``n_fft // 4``.  rate > 1 is faster and shorter.
+    A list of device tensors.  n_fft must be a multiple of 16 and hop_length of 4, ``transform="fft"`` takes powers of two from
+    32 to 4096, a signal must be longer than ``n_fft // 2`` samples: the STFT's and ISTFT's own errors say so."""
+    wavs = _check_signals(wavs, "time_stretch")
+    rates = _check_rates(rates, len(wavs), "time_stretch")
+    _transform_id(transform)
+    n_fft = int(n_fft)
+    hop_length = n_fft // 4 if hop_length is None else int(hop_length)
+    win_length = n_fft if win_length is None else int(win_length)
+    fwd, inv = _stretch_engines(n_fft, hop_length, win_length, window, transform, device)
+    ctx = Context.get(device)
+    lens, x = _pack_ragged(ctx, wavs, "time_stretch")
+    B, nb = len(lens), fwd.n_bin
+    nf = [fwd.frames(n) for n in lens]
+    spec = ctx.empty((sum(nf), 2 * nb))
+    _capi.check(ctx.lib.pk_mel_run(fwd.h, dptr(x), _i32p(lens), B, dptr(spec), 0, 0))
+    rows, nt = _pvoc_packed(ctx, spec, nf, rates, nb)
+    ns = [inv.samples(t) for t in nt]
+    y = ctx.empty((max(1, sum(ns)),))
+    _capi.check(ctx.lib.pk_istft_run(inv.h, dptr(rows), _i32p(np.asarray(nt, dtype=np.int32)), B, dptr(y), 0))
+    return [wrap(_fit_length(p, stretched_length(n, r))) for p, n, r in zip(torch.split(y[:sum(ns)], ns), lens, rates)]
+
+
+def time_stretch(y, rate, **kw):
+    return time_stretch_batch([y], [rate], **kw)[0]
+
+
+def pitch_shift_ratio(n_steps, bins_per_octave=12):
+    """(Fraction, cents_off): the rational nearest the stretch rate ``2 ** (-n_steps / bins_per_octave)`` with a denominator of
+    at most 1000 (``Fraction.limit_denominator``), and how far the shift it realises is from the one asked for, in cents
+    (positive: sharp).  Exact for whole octaves; within 0.027 cent for every integer step within two octaves at 12 and 24 bins
+    per octave."""
+    if int(bins_per_octave) != bins_per_octave or bins_per_octave < 1:
+        raise ValueError(f"pitch_shift: bins_per_octave = {bins_per_octave!r} must be a positive integer")
+    try:
+        steps = float(n_steps)
+    except (TypeError, ValueError):
+        raise ValueError(f"pitch_shift: n_steps = {n_steps!r} is not a number") from None
+    if not math.isfinite(steps):
+        raise ValueError(f"pitch_shift: n_steps = {steps} must be finite")
+    try:
+        rate = 2.0 ** (-steps / int(bins_per_octave))
+    except OverflowError:
+        rate = math.inf
+    if not math.isfinite(rate) or not rate > 0.0:
+        raise ValueError(f"pitch_shift: n_steps = {steps} at {bins_per_octave} bins per octave is no usable ratio")
+    fr = Fraction(rate).limit_denominator(PITCH_SHIFT_MAX_DENOMINATOR)
+    if fr <= 0:
+        raise ValueError(f"pitch_shift: n_steps = {steps} at {bins_per_octave} bins per octave is no usable ratio")
+    return fr, 1200.0 * math.log2(rate / (fr.numerator / fr.denominator))
+
+
+def pitch_shift_batch(wavs, sr, n_steps, bins_per_octave=12, res_type="kaiser_best", device=None, **stft_kw):
+    """``librosa.effects.pitch_shift`` for a ragged list of signals, one shift for the batch: a time stretch by the rational rate
+    p / q of ``pitch_shift_ratio`` and then ``audio.Resample`` at that same ratio (up / down = p / q in lowest terms: librosa's
+    ``resample(orig_sr=sr / rate, target_sr=sr)``), each result cropped or zero-padded to its input's length.  The resampler is
+    THIS PROJECT'S filter, not librosa's.  ``sr`` enters no arithmetic (the ratio does not depend on it); it is
+    checked.  ``n_steps = 0`` returns the inputs as they are, without an engine call; a ratio outside ``Resample``'s envelope
+    raises its ``NotImplementedError``.  ``stft_kw``: n_fft, hop_length, win_length, window, transform of ``time_stretch``."""
+    wavs = _check_signals(wavs, "pitch_shift")
+    if not (isinstance(sr, (int, float, np.integer, np.floating)) and math.isfinite(sr) and sr > 0):
+        raise ValueError(f"pitch_shift: sr = {sr!r} must be a positive number")
+    fr, _ = pitch_shift_ratio(n_steps, bins_per_octave)
+    if float(n_steps) == 0.0:
+        ctx = Context.get(device)
+        return [wrap(ctx.to_device(w)) for w in wavs]
+    rs = _resampler(fr.denominator, fr.numerator, res_type=res_type, device=device)        # the envelope is checked here
+    out = rs.run_batch(time_stretch_batch(wavs, fr.numerator / fr.denominator, device=device, **stft_kw))
+    return [wrap(_fit_length(o.as_subclass(torch.Tensor), int(w.shape[0]))) for o, w in zip(out, wavs)]
+
+
+def pitch_shift(y, sr, n_steps, bins_per_octave=12, res_type="kaiser_best", **kw):
+    return pitch_shift_batch([y], sr, n_steps, bins_per_octave, res_type, **kw)[0]
 
 
 def _decode_wav(data):

@@ -167,6 +167,7 @@ struct pk_ctx_scratch {
     pk_dbuf stoi_ws;
     pk_dbuf iir_tab;     // iir.hip: the call's table; the chunk states, loudness pieces, peaks and hop segments of a call (pk_iir.h)
     pk_dbuf iir_ws;
+    pk_dbuf pvoc_tab;    // pvoc.hip: the call's table
 };
 pk_ctx_scratch* pk_ctx_get_scratch(pk_ctx* ctx);
 

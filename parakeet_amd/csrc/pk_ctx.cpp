@@ -104,6 +104,7 @@ extern "C" void pk_ctx_destroy(pk_ctx* ctx) {
         kv.second->stoi_ws.release();
         kv.second->iir_tab.release();
         kv.second->iir_ws.release();
+        kv.second->pvoc_tab.release();
         delete kv.second;
     }
     for (void* t : ctx->rfft_tw)
