@@ -1033,6 +1033,70 @@ int pk_pwgd_set_debug(pk_pwgd* h, int32_t on);
 int pk_pwgd_debug_read(pk_pwgd* h, int32_t layer, int32_t b, float* host_out, int64_t n_floats);
 void pk_pwgd_destroy(pk_pwgd* h);
 
+/* ------------------------------------------------------- HiFi-GAN generator */
+/* The generator of HiFi-GAN (Kong et al. 2020), restated from the paper with the module layout of the usual
+ * HiFiGANGenerator; NEITHER THE PARAMETER NAMES NOR THE OUTPUT SLOPE BELOW COULD BE CHECKED AGAINST A REAL CHECKPOINT.
+ * With ch_i = channels >> i and a_s = LeakyReLU(s):
+ *   x = Conv1D(in_channels -> channels, kernel_size)(mel)                                            "input_conv"
+ *   per stage i (scale s_i): x = Conv1DTranspose(ch_i -> ch_(i+1), 2 s_i, stride s_i, padding s_i / 2 + s_i % 2,
+ *                                output_padding s_i % 2)(a_slope(x))                                 "upsamples.{i}.1"
+ *     per residual block j (kernel k_j), y = x, for its n-th dilation d:
+ *       t = Conv1D(k_j, dilation d)(a_slope(y))                                                      "blocks.{i nb + j}.convs1.{n}.1"
+ *       use_additional_convs: t = Conv1D(k_j)(a_slope(t))                                            "blocks.{i nb + j}.convs2.{n}.1"
+ *       y = t + y
+ *     x = (sum_j y_j) / nb
+ *   wav = tanh(Conv1D(ch_last -> 1, kernel_size)(a_0.01(x)))                                         "output_conv.1"
+ * Every convolution zero-pads its own input at the two ends of the utterance.  Weights: Conv1D (C_out, C_in, k),
+ * Conv1DTranspose (C_in, C_out, k); ".weight", or ".weight_g" / ".weight_v" folded at finalize (norm over all axes but 0).
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): in_channels 1 ... 512, out_channels 1; kernel_size odd
+ * 3 ... 11; 1 ... 6 stages with scales 2 ... 16 and upsample_kernel_sizes[i] == 2 * upsample_scales[i]; hop 4 ... 1024; every
+ * ch_i a multiple of 8 in 8 ... 512; 1 ... 4 residual blocks with odd kernels 3 ... 11 and 1 ... 4 dilations each,
+ * (k - 1) / 2 * d <= 64; bias = 1. */
+#define PK_HFG_MAX_STAGES 6
+#define PK_HFG_MAX_BLOCKS 4
+#define PK_HFG_MAX_DILS 4
+typedef struct pk_hfg pk_hfg;
+typedef struct {
+    int32_t in_channels;                  /* 80 */
+    int32_t out_channels;                 /* 1 */
+    int32_t channels;                     /* 512 */
+    int32_t kernel_size;                  /* 7 */
+    int32_t n_upsample;                   /* 4 */
+    int32_t upsample_scales[PK_HFG_MAX_STAGES];         /* 8, 8, 2, 2 */
+    int32_t upsample_kernel_sizes[PK_HFG_MAX_STAGES];   /* 16, 16, 4, 4 */
+    int32_t n_blocks;                     /* 3 */
+    int32_t resblock_kernel_sizes[PK_HFG_MAX_BLOCKS];   /* 3, 7, 11 */
+    int32_t n_dilations[PK_HFG_MAX_BLOCKS];             /* 3, 3, 3 */
+    int32_t resblock_dilations[PK_HFG_MAX_BLOCKS][PK_HFG_MAX_DILS];   /* 1, 3, 5 each */
+    int32_t use_additional_convs;         /* 1 */
+    int32_t bias;                         /* 1 */
+    float negative_slope;                 /* 0.1 */
+} pk_hfg_cfg;
+int pk_hfg_create(pk_ctx* ctx, const pk_hfg_cfg* cfg, pk_hfg** out);
+int pk_hfg_set_param(pk_hfg* h, const char* name, const float* data, const int64_t* shape, int32_t ndim);
+int pk_hfg_finalize(pk_hfg* h);
+/* PK_PWG_MATH_F16X3 (default; the activations' block scale is one exponent per utterance and layer input, measured by the
+ * layer that produced it; the weights carry one exponent per tensor) or PK_PWG_MATH_F32.  PK_PWG_MATH_BF16X3: PK_EUNSUPPORTED. */
+int pk_hfg_set_math(pk_hfg* h, int32_t mode);
+/* ZScore statistics of in_channels elements, applied ((x - mu) / sigma) only by calls with PK_APPLY_NORMALIZER; NULL, NULL: none. */
+int pk_hfg_set_normalizer(pk_hfg* h, const float* mu, const float* sigma, int32_t n);
+/* mel: packed (sum frames, in_channels); frames (B, host) >= 1 each; wav_out: packed (sum frames * hop).  An utterance's
+ * samples are bit-identical alone, in any batch and at any position in it.  The workspace is sized per call from the frame
+ * counts; a call that would need more than 16 GiB of activations returns PK_ENOMEM (split the batch; chunking one long
+ * utterance is not implemented).  flags: PK_APPLY_NORMALIZER, PK_HOST_IO (mel and wav_out are host pointers; synchronous). */
+int pk_hfg_infer(pk_hfg* h, const float* mel, const int32_t* frames, int32_t B, float* wav_out, int32_t flags);
+/* Test tap: the output of stage `stage` (0 ... n_upsample - 1) after its block mean, of utterance b of the last
+ * pk_hfg_infer, copied to HOST as (channels >> (stage + 1), frames[b] * scales up to the stage) channel-major; n_floats =
+ * that many (else PK_ESHAPE).  Runs the stack again over that utterance in the handle's current math.  PK_ESTATE without
+ * a pk_hfg_infer since the parameters were last set. */
+int pk_hfg_debug_read(pk_hfg* h, int32_t stage, int32_t b, float* host_out, int64_t n_floats);
+/* Test tap of one convolution: what launch `launch` of the stack wrote for utterance b of the last pk_hfg_infer, to HOST as
+ * (C_out, positions) channel-major.  Launches in order: input_conv; per stage the transposed convolution, then per residual
+ * block and dilation convs1 (t), with use_additional_convs convs2 (t + y; the block's last one writes the running block
+ * mean instead); the output convolution's wav is what pk_hfg_infer returns.  Runs the stack again up to that launch. */
+int pk_hfg_debug_conv(pk_hfg* h, int32_t launch, int32_t b, float* host_out, int64_t n_floats);
+void pk_hfg_destroy(pk_hfg* h);
+
 /* ------------------------------------------------- masked L1 + SSIM of mel pairs */
 /* The two spectrogram terms of the SpeedySpeech evaluator (speedyspeech_updater.py:119-140) in one pass over both
  * images, and parakeet/modules/ssim.py:21-61 (channel = 1) as a metric of its own.

@@ -147,6 +147,15 @@ class PwgdCfg(C.Structure):
                                           "dilation_factor")] + [("negative_slope", C.c_float), ("bias", C.c_int32)])
 
 
+class HfgCfg(C.Structure):
+    """pk_hfg_cfg"""
+    _fields_ = ([(n, C.c_int32) for n in ("in_channels", "out_channels", "channels", "kernel_size", "n_upsample")] +
+                [("upsample_scales", C.c_int32 * 6), ("upsample_kernel_sizes", C.c_int32 * 6), ("n_blocks", C.c_int32),
+                 ("resblock_kernel_sizes", C.c_int32 * 4), ("n_dilations", C.c_int32 * 4),
+                 ("resblock_dilations", (C.c_int32 * 4) * 4), ("use_additional_convs", C.c_int32), ("bias", C.c_int32),
+                 ("negative_slope", C.c_float)])
+
+
 class OpGemmCfg(C.Structure):
     """pk_op_gemm_cfg"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "res", "a_amax", "a2_amax", "rowvalid", "out_rowmap", "C", "C2",
@@ -329,6 +338,15 @@ def _declare(lib):
         "pk_pwgd_set_debug": (C.c_int, [vp, i32]),
         "pk_pwgd_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_pwgd_destroy": (None, [vp]),
+        "pk_hfg_create": (C.c_int, [vp, C.POINTER(HfgCfg), C.POINTER(vp)]),
+        "pk_hfg_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),
+        "pk_hfg_finalize": (C.c_int, [vp]),
+        "pk_hfg_set_math": (C.c_int, [vp, i32]),
+        "pk_hfg_set_normalizer": (C.c_int, [vp, f32p, f32p, i32]),
+        "pk_hfg_infer": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_hfg_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
+        "pk_hfg_debug_conv": (C.c_int, [vp, i32, i32, f32p, i64]),
+        "pk_hfg_destroy": (None, [vp]),
         "pk_mel_loss_run": (C.c_int, [vp, f32p, f32p, i32p, i32p, i32, i32, i32, C.c_void_p, f32p, i32]),
         "pk_pair_loss_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i64, i64, i32p, i32, i32, C.c_void_p, i32]),
         "pk_bce_logits_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i32p, i32, C.c_float, C.c_void_p, i32]),

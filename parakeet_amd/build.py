@@ -50,11 +50,11 @@ _NO_CONTRACT = ["-ffp-contract=off"]
 FILE_FLAGS = {"wf_layer.hip": _UNROLL_ALL, "ffn_planes.hip": _UNROLL_ALL, "ops.hip": _NO_SLP, "speedyspeech.hip": _NO_SLP,
               "tts.hip": _NO_SLP, "tts_teacher.hip": _NO_SLP, "taco2.hip": _NO_SLP, "pwg_gen.hip": _NO_SLP, "mel_loss.hip": _NO_SLP,
               "pwg_disc.hip": _NO_SLP, "spk_loss.hip": _NO_SLP, "resample.hip": _NO_SLP, "pitch.hip": _NO_SLP, "align.hip": _NO_SLP, "stats.hip": _NO_SLP,
-              "rfft.hip": _NO_SLP,
+              "rfft.hip": _NO_SLP, "hifigan.hip": _NO_SLP,
               "dtw.hip": _NO_SLP + _NO_CONTRACT, "stoi.hip": _NO_SLP + _NO_CONTRACT, "iir.hip": _NO_SLP + _NO_CONTRACT,
               "pvoc.hip": _NO_SLP + _NO_CONTRACT}
 ISA_DIR = os.path.join(CSRC, "_isa")   # the product build's device assembly, one .s per source (kept for tools/pk_opsel_lint.py and the ISA tools)
-SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "rfft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "edit.hip", "stoi.hip", "iir.hip", "pvoc.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
+SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "rfft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "edit.hip", "stoi.hip", "iir.hip", "pvoc.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "hifigan.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
 
 
 def hipcc():

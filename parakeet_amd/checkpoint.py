@@ -227,6 +227,21 @@ def load_pwg(config, checkpoint, stats):
     return PWGInference(ZScore(mu, sigma), vocoder)
 
 
+def load_hifigan(config, checkpoint, stats):
+    """A HiFi-GAN vocoder from a recipe's yaml (``generator_params``), a snapshot archive (``generator_params``) and the
+    mel statistics, as ``load_pwg``: returns ``HiFiGANInference``.  The parameter names the engine expects are listed in
+    parakeet_amd/hifigan.py; they could not be checked against a real checkpoint."""
+    from .hifigan import HiFiGANGenerator, HiFiGANInference
+    from .normalizer import ZScore
+    cfg = _config(config)
+    vocoder = HiFiGANGenerator(**cfg["generator_params"])
+    vocoder.set_state_dict(load_params(checkpoint, "generator_params"))
+    vocoder.remove_weight_norm()
+    vocoder.eval()
+    mu, sigma = load_stats(stats)
+    return HiFiGANInference(ZScore(mu, sigma), vocoder)
+
+
 def load_pwg_discriminator(config, checkpoint):
     """The discriminator a Parallel WaveGAN snapshot carries beside its generator (``models['discriminator']`` of
     examples/parallel_wavegan/baker/train.py, saved as ``discriminator_params``): returns ``PWGDiscriminator`` built from the

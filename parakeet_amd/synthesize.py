@@ -19,7 +19,8 @@ class Synthesizer:
     def __init__(self, fastspeech2_inference, pwg_inference, acoustic_lanes=()):
         self.am_inference, self.voc_inference = fastspeech2_inference, pwg_inference
         self.am = fastspeech2_inference.acoustic_model
-        self.voc = pwg_inference.pwg_generator
+        # a HiFiGANInference names its vocoder `generator`; PWGInference, as in the reference, `pwg_generator`
+        self.voc = getattr(pwg_inference, "generator", None) or pwg_inference.pwg_generator
         self.hop = self.voc.upsample_factor
         # issue-ahead lanes (see issue_acoustic): lane 0 is the acoustic model itself; further lanes are wrappers around OTHER
         # engine handles holding the same weights, each with its own side stream

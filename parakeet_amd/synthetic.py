@@ -225,6 +225,47 @@ def pwg_state(cfg=None, seed=42, weight_norm=False):
     return st
 
 
+HIFIGAN_V1 = dict(   # HiFi-GAN V1 (Kong et al. 2020, table 5) at hop 256
+    in_channels=80, out_channels=1, channels=512, kernel_size=7, upsample_scales=(8, 8, 2, 2),
+    upsample_kernel_sizes=(16, 16, 4, 4), resblock_kernel_sizes=(3, 7, 11), resblock_dilations=((1, 3, 5),) * 3,
+    use_additional_convs=True, bias=True, nonlinear_activation="LeakyReLU",
+    nonlinear_activation_params={"negative_slope": 0.1}, use_weight_norm=True)
+
+
+def hifigan_state(cfg=None, seed=11, weight_norm=False):
+    """Seeded HiFiGANGenerator state dict under the names of parakeet_amd/hifigan.py: weights N(0, 1) / sqrt(fan_in) (x 0.7
+    in the residual blocks, so that a block's output stays at its input's size), biases 0.1 N(0, 1).  ``weight_norm``:
+    weight_g (C, 1, 1) with the rows' norms times a factor in [0.8, 1.25], weight_v the direction at another length."""
+    cfg = dict(HIFIGAN_V1, **(cfg or {}))
+    rng = np.random.default_rng(seed)
+    st = {}
+
+    def put(name, shape, fan_in, gain=1.0):
+        w = (rng.standard_normal(shape) * gain / math.sqrt(fan_in)).astype(np.float32)
+        if weight_norm:
+            norm = np.sqrt((w.astype(np.float64).reshape(shape[0], -1) ** 2).sum(1))
+            st[name + ".weight_g"] = (norm * rng.uniform(0.8, 1.25, size=shape[0])).astype(np.float32).reshape(-1, 1, 1)
+            st[name + ".weight_v"] = (w * rng.uniform(0.5, 2.0, size=(shape[0], 1, 1))).astype(np.float32)
+        else:
+            st[name + ".weight"] = w
+        nout = shape[1] if ".1" in name and name.startswith("upsamples") else shape[0]
+        st[name + ".bias"] = (0.1 * rng.standard_normal(nout)).astype(np.float32)
+
+    ch, k = cfg["channels"], cfg["kernel_size"]
+    put("input_conv", (ch, cfg["in_channels"], k), cfg["in_channels"] * k)
+    nb = len(cfg["resblock_kernel_sizes"])
+    for i, s in enumerate(cfg["upsample_scales"]):
+        cin, c = ch >> i, ch >> (i + 1)
+        put(f"upsamples.{i}.1", (cin, c, 2 * s), 2 * cin)   # two taps reach an output
+        for j, (kj, ds) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilations"])):
+            for n in range(len(ds)):
+                put(f"blocks.{i * nb + j}.convs1.{n}.1", (c, c, kj), c * kj, 0.7)
+                if cfg.get("use_additional_convs", True):
+                    put(f"blocks.{i * nb + j}.convs2.{n}.1", (c, c, kj), c * kj, 0.7)
+    put("output_conv.1", (1, ch >> len(cfg["upsample_scales"]), k), (ch >> len(cfg["upsample_scales"])) * k)
+    return st
+
+
 PWG_DISC_LJSPEECH = dict(   # discriminator_params of examples/parallel_wavegan/baker/conf/default.yaml
     in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1,
     nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, bias=True, use_weight_norm=True)
