@@ -332,7 +332,7 @@ typedef struct {
                                     * 64; 1 2 4 8 16 32 64 1 at 128.  Another even value: PK_EUNSUPPORTED (a KeyError there); odd:
                                     * PK_EINVAL (:586-589) */
     int32_t channels;              /* 64 (paper small model) / 128 (repo default) */
-    int32_t n_mels;                /* 80 */
+    int32_t n_mels;                /* 80; a multiple of 16 up to 256 (the upsampling kernel's block), else PK_EUNSUPPORTED */
     int32_t kernel_h, kernel_w;    /* 3, 3 */
 } pk_wf_cfg;
 
@@ -356,7 +356,9 @@ int pk_wf_set_math(pk_wf* h, int32_t mode);
  *                  measured slower than eight launches in round 4; PK_EUNSUPPORTED in the product, a measurement configuration of
  *                  the profile build, and there for n_group 8 / 16 only: the launch has one tap table for all its layers)
  *   "fuse_step"    1 (default) = a row's affine step and the next row's input projection happen in the launch of its last
- *                  layer; 0 = in a kernel of their own */
+ *                  layer; 0 = in a kernel of their own
+ *   "keep_cond"    0 (default); 1 = pk_wf_infer on the fused layer kernel, which turns the upsampled condition into fp16 planes in
+ *                  place, first keeps a copy of it for pk_wf_debug_read (a test tap: one more buffer and a copy per call) */
 int pk_wf_set_option(pk_wf* h, const char* key, int64_t value);
 int pk_wf_finalize(pk_wf* h);
 /* For t_mel frames: length of the trimmed upsampled condition (= length of the z the reference
@@ -387,6 +389,12 @@ int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, int32_t B, co
 int pk_wf_forward_length(pk_wf* h, int32_t t_mel, int32_t n_audio, int32_t* z_len);
 int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, const float* audio, const int32_t* audio_len, int32_t B,
                   float* z, double* logdet, int32_t flags);
+/* Test tap of the last pk_wf_infer / pk_wf_forward for utterance b, copied to host: what = 0 is the upsampled condition as the
+ * flows read it, (n_mels, wav_len) in natural time order -- after pk_wf_infer the trimmed upsampling cut to wav_len, after
+ * pk_wf_forward the untrimmed one cut to the z length.  Un-folds both layouts of the condition buffer ([pos][mp] and the fused
+ * path's blocks of 32 positions).  PK_ESTATE before a call has run, and after a pk_wf_infer on the fused layer kernel without
+ * option "keep_cond". */
+int pk_wf_debug_read(pk_wf* h, int32_t what, int32_t b, float* host_out, int64_t n_floats);
 void pk_wf_destroy(pk_wf* h);
 
 /* ------------------------------------------------------------ SpeedySpeech */

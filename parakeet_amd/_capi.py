@@ -18,6 +18,7 @@ PROFILE_LIB = os.environ.get("PK_PROFILE_LIB", "0") not in ("", "0")
 LIB_PATH = os.path.join(_HERE, "libpk_synth_prof.so" if PROFILE_LIB else "libpk_synth.so")
 
 PK_OK = 0
+PK_EUNSUPPORTED = -3       # include/pk_synth.h pk_status: configuration not implemented
 PK_HOST_IO = 1
 PK_PWG_C_HAS_CONTEXT = 2
 PK_APPLY_NORMALIZER = 4
@@ -234,6 +235,7 @@ def _declare(lib):
         "pk_wf_infer": (C.c_int, [vp, f32p, i32p, i32, f32p, f32p, i32]),
         "pk_wf_forward_length": (C.c_int, [vp, i32, i32, i32p]),
         "pk_wf_forward": (C.c_int, [vp, f32p, i32p, f32p, i32p, i32, f32p, C.c_void_p, i32]),
+        "pk_wf_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_wf_destroy": (None, [vp]),
         "pk_ss_create": (C.c_int, [vp, C.POINTER(SsCfg), C.POINTER(vp)]),
         "pk_ss_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),

@@ -33,6 +33,7 @@
 namespace {
 
 constexpr int WF_LEAD = 256;  // margin positions around every per-position buffer (>= largest tap shift)
+constexpr int WF_UP_THREADS = 256;   // block size of k_wf_upsample = the largest n_mels pk_wf_create accepts
 
 // One Conv2DTranspose(1,1,(3,2f),stride (1,f),padding (1,f//2)) + trim + leaky_relu(0.4) layer.
 // in[rows][M] (time-major, M mel bins), out likewise -- or, for the last layer, the folded
@@ -272,12 +273,21 @@ struct pk_wf {
                               // on 8 XCDs costs 11 us of serialised atomics + 16 - 27 us of L2 write-back / invalidate
                               // (tools/micro/grid_barrier.hip, profiles/r04_grid_barrier_micro.txt) against the 5 - 6 us between two
                               // dependent launches -- 1 089 us per row instead of 8 x 55.  Off by default.
+    bool keep_cond = false;   // option "keep_cond": pk_wf_infer on the fused kernel keeps a copy of the fp32 condition for pk_wf_debug_read
+    // what pk_wf_debug_read needs of the last pk_wf_infer / pk_wf_forward: where every utterance's condition lies
+    struct {
+        int dir = 0;             // 0 = no call yet, 1 = infer, 2 = forward
+        bool blocked = false;    // [pos / 32][mp][32] (the fused path) or [pos][mp]
+        const pk_dbuf* buf = nullptr;   // ws_cond, ws_condkeep, or nullptr: converted to planes in place and not kept
+        long row_stride = 0;     // floats per folded row
+        std::vector<int> woff, pruned;
+    } last;
     bool fuse_step = true;    // option "fuse_step": the row's step in the launch of its last layer (else a kernel of its own)
     std::vector<WfFlowW> flows;
     std::vector<size_t> up_w;
     std::vector<float> up_b;
     // workspace
-    pk_dbuf ws_tab, ws_mel, ws_z, ws_wav, ws_u[2], ws_cond, ws_cur, ws_nxt, ws_hist, ws_zbuf, ws_skip, ws_hamax, ws_camax, ws_trace, ws_bar, ws_desc, ws_replay;
+    pk_dbuf ws_tab, ws_mel, ws_z, ws_wav, ws_u[2], ws_cond, ws_cur, ws_nxt, ws_hist, ws_zbuf, ws_skip, ws_hamax, ws_camax, ws_trace, ws_bar, ws_desc, ws_replay, ws_condkeep;
     pk_dbuf ws_fa, ws_fb, ws_fam, ws_fcond, ws_fcam, ws_fprm, ws_fpart, ws_flogdet, ws_fz, ws_fskip;   // pk_wf_forward
     std::vector<WflLayer> desc_host;   // host image of ws_desc (kept until the next inference: the upload is asynchronous)
     const float* W(size_t off) const { return arena.as<float>() + off; }
@@ -299,8 +309,11 @@ extern "C" int pk_wf_create(pk_ctx* ctx, const pk_wf_cfg* cfg, pk_wf** out) {
     if (!dil_h) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: n_group %d has no height dilations (8, 16, 32, 64 or 128)", c.n_group);
     if (c.n_layers != 8) PK_FAIL(PK_EINVAL, "number of dilations_h should equals num of layers");  // :328-331
     if (c.kernel_h != 3 || c.kernel_w != 3) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: kernel_size must be (3, 3)");
-    if (c.channels % 64 != 0 || c.channels > 256) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: channels must be 64/128/192/256");
+    if (c.channels <= 0 || c.channels % 64 != 0 || c.channels > 256) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: channels must be 64/128/192/256");
     if (c.n_mels % PK_GEMM_BK != 0) PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: n_mels must be a multiple of 16");
+    // k_wf_upsample runs 256 / n_mels time steps per 256-thread block: beyond 256 mel bins that is none (no recipe has more than 80)
+    if (c.n_mels < PK_GEMM_BK || c.n_mels > WF_UP_THREADS)
+        PK_FAIL(PK_EUNSUPPORTED, "WaveFlow: n_mels %d unsupported (16 .. %d: the upsampling kernel holds one time step of all mel bins in a block)", c.n_mels, WF_UP_THREADS);
     if (c.n_upsample < 1 || c.n_upsample > 4) PK_FAIL(PK_EINVAL, "WaveFlow: 1..4 upsample layers");
     for (int i = 0; i < c.n_upsample; ++i)
         if (c.upsample_factors[i] < 2 || c.upsample_factors[i] % 2 || c.upsample_factors[i] > 64)
@@ -382,6 +395,7 @@ extern "C" int pk_wf_set_option(pk_wf* h, const char* key, int64_t value) {
         h->persistent = value != 0;
     }
     else if (strcmp(key, "fuse_step") == 0) h->fuse_step = value != 0;
+    else if (strcmp(key, "keep_cond") == 0) h->keep_cond = value != 0;
     else PK_FAIL(PK_EINVAL, "pk_wf_set_option: unknown option '%s'", key);
     return PK_OK;
 }
@@ -539,6 +553,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     if (!h || !mel || !frames || !wav) PK_FAIL(PK_EINVAL, "pk_wf_infer: NULL argument");
     if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_wf_infer: call pk_wf_finalize first");
     if (B <= 0) PK_FAIL(PK_EINVAL, "pk_wf_infer: batch size must be positive");
+    h->last.dir = 0;   // (a call that fails leaves nothing for pk_wf_debug_read)
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     const pk_wf_cfg& c = h->cfg;
@@ -686,9 +701,9 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
                     for (int b = 0; b < B; ++b) len[b] = c.upsample_factors[k] * len[b] - c.upsample_factors[k];
                 for (int b = 0; b < B; ++b) maxT = std::max(maxT, len[b]);
             }
-            const int tpb = 256 / M;  // time steps per block
+            const int tpb = WF_UP_THREADS / M;  // time steps per block (>= 1: pk_wf_create)
             dim3 grid(pk_div_up(maxT, tpb), 1, B);
-            PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(256), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i],
+            PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(WF_UP_THREADS), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i],
                       out, d_tab + o_outoff[i], h->W(h->up_w[i]), h->up_b[i], f, M, last ? G : 0, d_tab + o_woff,
                       d_tab + o_pruned, cond_row, MP, use_wfl ? 1 : 0, 1);
             in = out;
@@ -697,6 +712,19 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     unsigned* hbmax = h->ws_hamax.as<unsigned>() + WF_LEAD / WFL_BLK;   // block maxima (fused layer kernel)
     unsigned* cbmax = h->ws_camax.as<unsigned>() + WF_LEAD / WFL_BLK;
     auto hbmax_ptr = [&](int layer, int slot) { return hbmax + ((size_t)h->slot_base[layer] + slot) * bstride; };
+    h->last.blocked = use_wfl;   // (last.dir stays 0 until the call has gone through)
+    h->last.buf = &h->ws_cond;
+    h->last.row_stride = cond_row;
+    h->last.woff = woff;
+    h->last.pruned = pruned;
+    if (use_wfl) {   // the planes replace the fp32 condition: the debug tap reads a copy, made on request only
+        h->last.buf = nullptr;
+        if (h->keep_cond) {
+            PK_TRY(h->ws_condkeep.reserve((size_t)G * cond_row * 4));
+            PK_HIP(hipMemcpyAsync(h->ws_condkeep.p, h->ws_cond.p, (size_t)G * cond_row * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            h->last.buf = &h->ws_condkeep;
+        }
+    }
     if (use_wfl) PK_TRY(wfl_cond_planes_launch(ctx, cond, cond_row, G, npos_alloc / WFL_BLK, bstride, cbmax, M));   // in place
     else if (split_math) PK_TRY(pk_row_amax_launch(ctx, cond, MP, MP, 0, (long)G * pstride - WF_LEAD, camax));
     // ---- fold z
@@ -1024,6 +1052,7 @@ extern "C" int pk_wf_infer(pk_wf* h, const float* mel, const int32_t* frames, in
     } else if (flags & PK_HOST_IO) {
         PK_HIP(hipStreamSynchronize(ctx->stream));
     }
+    h->last.dir = 1;   // the whole call went through: the record above is valid for pk_wf_debug_read
     return PK_OK;
 }
 
@@ -1058,6 +1087,7 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
     if (!h || !mel || !frames || !audio || !audio_len || !z || !logdet) PK_FAIL(PK_EINVAL, "pk_wf_forward: NULL argument");
     if (!h->finalized) PK_FAIL(PK_ESTATE, "pk_wf_forward: call pk_wf_finalize first");
     if (B <= 0) PK_FAIL(PK_EINVAL, "pk_wf_forward: batch size must be positive");
+    h->last.dir = 0;
     pk_ctx* ctx = h->ctx;
     PK_DEVICE(ctx->device);
     const pk_wf_cfg& c = h->cfg;
@@ -1210,14 +1240,19 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
             const int f = c.upsample_factors[i];
             const bool last = i == c.n_upsample - 1;
             float* out = last ? cond : h->ws_u[i & 1].as<float>();
-            const int tpb = 256 / M;
+            const int tpb = WF_UP_THREADS / M;   // >= 1: pk_wf_create
             dim3 grid(pk_div_up(up_maxT[i], tpb), 1, B);
-            PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(256), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i], out,
+            PK_LAUNCH(ctx, "wf_upsample", k_wf_upsample, grid, dim3(WF_UP_THREADS), 0, in, d_tab + o_inoff[i], d_tab + o_inlen[i], out,
                       d_tab + o_outoff[i], h->W(h->up_w[i]), h->up_b[i], f, M, last ? G : 0, d_tab + o_woff, d_tab + o_pruned,
                       cond_row, MP, use_wfl ? 1 : 0, 0);
             in = out;
         }
     }
+    h->last.blocked = use_wfl;
+    h->last.buf = &h->ws_cond;   // (the planes of the fused path are a buffer of their own: ws_fcond)
+    h->last.row_stride = cond_row;
+    h->last.woff = woff;
+    h->last.pruned = pruned;
     // ---- fold the audio (:653-654)
     PK_LAUNCH(ctx, "wf_fold", k_wf_fold, dim3(pk_div_up(npos, 256)), dim3(256), 0, d_audio, putt_flat, d_tab + o_pw, d_tab + o_aoff,
               G, npos, pstride, cur);
@@ -1369,6 +1404,43 @@ extern "C" int pk_wf_forward(pk_wf* h, const float* mel, const int32_t* frames, 
         PK_HIP(hipMemcpyAsync(logdet, d_logdet, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PK_HIP(hipStreamSynchronize(ctx->stream));
     }
+    h->last.dir = 2;
+    return PK_OK;
+}
+
+/* what: 0 = the condition of utterance b as the last pk_wf_infer / pk_wf_forward upsampled it, (n_mels, pruned_len) in natural time
+ * order: sample t sits in the folded row t % n_group at position woff[b] + t / n_group.  The flows permute the rows by index maps,
+ * so the buffer stays in the upsampler's order. */
+extern "C" int pk_wf_debug_read(pk_wf* h, int32_t what, int32_t b, float* host_out, int64_t n_floats) {
+    if (!h || !host_out) PK_FAIL(PK_EINVAL, "pk_wf_debug_read: NULL argument");
+    if (h->last.dir == 0) PK_FAIL(PK_ESTATE, "pk_wf_debug_read: no pk_wf_infer or pk_wf_forward has run");
+    if (what != 0) PK_FAIL(PK_EINVAL, "pk_wf_debug_read: unknown tap %d", what);
+    if (!h->last.buf)
+        PK_FAIL(PK_ESTATE, "pk_wf_debug_read: pk_wf_infer on the fused layer kernel turns the condition into fp16 planes in place; set option "
+                           "'keep_cond' before the call");
+    if (b < 0 || b >= (int)h->last.woff.size()) PK_FAIL(PK_EINVAL, "pk_wf_debug_read: utterance out of range");
+    pk_ctx* ctx = h->ctx;
+    PK_DEVICE(ctx->device);
+    const int M = h->cfg.n_mels, G = h->cfg.n_group, MP = h->mp;
+    const int T = h->last.pruned[b], W = T / G, w0 = h->last.woff[b];
+    if (n_floats != (int64_t)M * T) PK_FAIL(PK_ESHAPE, "pk_wf_debug_read: expected %ld floats, got %lld", (long)M * T, (long long)n_floats);
+    // per folded row: the whole 32-position blocks (or the positions) that hold the utterance
+    const long p_lo = h->last.blocked ? (long)(w0 / WFL_BLK) * WFL_BLK : w0;
+    const long p_hi = h->last.blocked ? (long)((w0 + W + WFL_BLK - 1) / WFL_BLK) * WFL_BLK : w0 + W;
+    const size_t n_row = (size_t)(p_hi - p_lo) * MP;
+    std::vector<float> row(n_row);
+    PK_HIP(hipStreamSynchronize(ctx->stream));
+    const float* cond = h->last.buf->as<float>() + (size_t)WF_LEAD * MP;
+    for (int r = 0; r < G; ++r) {
+        PK_HIP(hipMemcpy(row.data(), cond + (size_t)r * h->last.row_stride + (size_t)p_lo * MP, n_row * 4, hipMemcpyDeviceToHost));
+        for (int w = 0; w < W; ++w) {
+            const long q = w0 + w - p_lo;
+            for (int c = 0; c < M; ++c) {
+                const size_t off = h->last.blocked ? (size_t)(q >> 5) * ((size_t)MP * WFL_BLK) + (size_t)c * WFL_BLK + (q & 31) : (size_t)q * MP + c;
+                host_out[(size_t)c * T + (size_t)w * G + r] = row[off];
+            }
+        }
+    }
     return PK_OK;
 }
 
@@ -1378,7 +1450,7 @@ extern "C" void pk_wf_destroy(pk_wf* h) {
     (void)hipStreamSynchronize(h->ctx->stream);
     pk_dbuf* bufs[] = {&h->arena, &h->arena16, &h->ws_tab, &h->ws_mel, &h->ws_z, &h->ws_wav, &h->ws_u[0], &h->ws_u[1],
                        &h->ws_cond, &h->ws_cur, &h->ws_nxt, &h->ws_hist, &h->ws_zbuf, &h->ws_skip,
-                       &h->ws_hamax, &h->ws_camax, &h->ws_trace, &h->ws_bar, &h->ws_desc, &h->ws_replay,
+                       &h->ws_hamax, &h->ws_camax, &h->ws_trace, &h->ws_bar, &h->ws_desc, &h->ws_replay, &h->ws_condkeep,
                        &h->ws_fa, &h->ws_fb, &h->ws_fam, &h->ws_fcond, &h->ws_fcam, &h->ws_fprm, &h->ws_fpart, &h->ws_flogdet, &h->ws_fz,
                        &h->ws_fskip};
     for (auto* b : bufs) b->release();

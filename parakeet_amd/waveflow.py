@@ -59,6 +59,7 @@ class ConditionalWaveFlow:
         self._h = h
         self._finalized = False
         self._math = "f16x3"
+        self._last_len = None    # per utterance: length of the condition the last call kept (debug_tap)
 
     @classmethod
     def from_pretrained(cls, config, checkpoint_path):
@@ -91,8 +92,33 @@ class ConditionalWaveFlow:
         self._math = mode
 
     def set_option(self, key, value):
-        """Named integer options of the engine handle (include/pk_synth.h, pk_wf_set_option): 'layer_waves'."""
+        """Named integer options of the engine handle (include/pk_synth.h, pk_wf_set_option): 'layer_waves', 'fuse_step',
+        'keep_cond'."""
         _capi.check(self._ctx.lib.pk_wf_set_option(self._h, key.encode(), int(value)))
+
+    def _auto_cast(self):
+        """Inside ``with parakeet_amd.amp.auto_cast():`` (examples/waveflow/synthesize.py:40) a call runs with fp16 operands --
+        where the model has that mode: it lives on the fused layer kernel, and the engine answers PK_EUNSUPPORTED for every other
+        model, which then runs with its own math (the reference's auto_cast works for any model).  True if the math was switched."""
+        if not amp.enabled() or self._math == "f16":
+            return False
+        status = self._ctx.lib.pk_wf_set_math(self._h, _MATH["f16"])
+        if status == _capi.PK_EUNSUPPORTED:
+            return False
+        _capi.check(status)
+        return True
+
+    def debug_tap(self, what, b):
+        """Test tap of the last infer_batch / forward_batch: ``"cond"`` is utterance ``b``'s upsampled mel as the flows read it,
+        (n_mels, T) in time order with T the length of that call's result (pk_wf_debug_read).  After an ``infer`` on the fused
+        layer kernel it needs ``set_option("keep_cond", 1)`` before the call."""
+        if what != "cond":
+            raise ValueError(f"unknown tap {what!r}")
+        known = self._last_len is not None and 0 <= b < len(self._last_len)
+        n = self._last_len[b] if known else 0    # (before a call, or no such utterance: the engine refuses, whatever the size)
+        out = np.empty((self.n_mels, n), dtype=np.float32)
+        _capi.check(self._ctx.lib.pk_wf_debug_read(self._h, 0, int(b), _capi.fptr(out), out.size))
+        return out
 
     def set_seed(self, seed):
         """Seed of the engine's own latent stream (``pk_randn``), used when neither ``z`` nor a torch
@@ -120,10 +146,8 @@ class ConditionalWaveFlow:
             z = torch.cat([ctx.to_device(v).reshape(-1) for v in zs])
         assert z is None or z.numel() == total_z, "z must have cond_len samples per utterance"
         wav = ctx.empty((sum(b for _, b in lens),))
-        # inside `with parakeet_amd.amp.auto_cast():` (examples/waveflow/synthesize.py:40) the call runs with fp16 operands
-        cast = amp.enabled() and self._math != "f16"
-        if cast:
-            _capi.check(ctx.lib.pk_wf_set_math(self._h, _MATH["f16"]))
+        cast = self._auto_cast()
+        self._last_len = [b for _, b in lens]
         try:
             _capi.check(ctx.lib.pk_wf_infer(self._h, dptr(mel), frames.ctypes.data_as(C.POINTER(C.c_int32)), len(mels),
                                             None if z is None else dptr(z), dptr(wav), 0))
@@ -160,9 +184,8 @@ class ConditionalWaveFlow:
         audio = torch.cat(auds).contiguous()
         z = ctx.empty((sum(zlen),))
         logdet = ctx.empty((len(mels),), dtype=torch.float64)
-        cast = amp.enabled() and self._math != "f16"   # as infer_batch: fp16 operands inside amp.auto_cast
-        if cast:
-            _capi.check(ctx.lib.pk_wf_set_math(self._h, _MATH["f16"]))
+        cast = self._auto_cast()
+        self._last_len = list(zlen)
         try:
             i32p = C.POINTER(C.c_int32)
             _capi.check(ctx.lib.pk_wf_forward(self._h, dptr(mel), frames.ctypes.data_as(i32p), dptr(audio), alen.ctypes.data_as(i32p),
