@@ -1105,6 +1105,104 @@ int pk_hfg_debug_read(pk_hfg* h, int32_t stage, int32_t b, float* host_out, int6
 int pk_hfg_debug_conv(pk_hfg* h, int32_t launch, int32_t b, float* host_out, int64_t n_floats);
 void pk_hfg_destroy(pk_hfg* h);
 
+/* ------------------------------------------------------- pseudo-QMF bank */
+/* The analysis / synthesis filter bank of multi-band MelGAN (csrc/pk_pqmf.h defines the arithmetic, tests/pqmf_ref.py
+ * restates it).  Filters, computed once on the host in float64 and rounded once to float32; K = subbands, n = 0 ... taps,
+ * c = n - taps / 2:
+ *   proto[n]       = sin(pi cutoff c) / (pi c) * kaiser(taps + 1, beta)[n]; the centre tap is cutoff
+ *   analysis_k[n]  = 2 proto[n] cos((2 k + 1) pi / (2 K) c + (-1)^k pi / 4)
+ *   synthesis_k[n] = the same with - (-1)^k pi / 4
+ * analysis: wav (L) -> bands (K, floor(L / K)), the zero-padded (taps / 2 each side) correlation with analysis_k taken at
+ * every K-th sample.  synthesis: bands (K, M) -> wav (K M): K - 1 zeros between samples, scaled by K, zero-padded by
+ * taps / 2, correlated with synthesis_k and summed over k; evaluated in its polyphase form, ceil((taps + 1) / K) products
+ * per band and sample at most.  Every product is one fmaf in a fixed order (pk_pqmf.h): a sample is bit-identical alone,
+ * in any batch and at any position in it.  No atomics.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): subbands 2 ... 16, taps even 4 ... 254, cutoff_ratio in
+ * (0, 0.5), beta 0 ... 700 (beyond, I0(beta) is no float64). */
+typedef struct pk_pqmf pk_pqmf;
+typedef struct {
+    int32_t subbands;                     /* 4 */
+    int32_t taps;                         /* 62 */
+    float cutoff_ratio;                   /* 0.142 */
+    float beta;                           /* 9.0 */
+} pk_pqmf_cfg;
+int pk_pqmf_create(pk_ctx* ctx, const pk_pqmf_cfg* cfg, pk_pqmf** out);
+/* The float32 filters to HOST, (subbands, taps + 1) each; n_floats = subbands * (taps + 1) (else PK_ESHAPE). */
+int pk_pqmf_filters(pk_pqmf* q, float* analysis_out, float* synthesis_out, int64_t n_floats);
+/* wav: packed (sum lens); lens (B, host) >= subbands each (else PK_EINVAL); bands_out: per utterance a (subbands,
+ * floor(lens[b] / subbands)) channel-major block, the blocks packed in order.  flags: PK_HOST_IO (synchronous). */
+int pk_pqmf_analysis(pk_pqmf* q, const float* wav, const int32_t* lens, int32_t B, float* bands_out, int32_t flags);
+/* bands: per utterance a (subbands, band_lens[b]) channel-major block, packed; band_lens (B, host) >= 1 each; wav_out:
+ * packed (sum band_lens * subbands).  flags: PK_HOST_IO (synchronous). */
+int pk_pqmf_synthesis(pk_pqmf* q, const float* bands, const int32_t* band_lens, int32_t B, float* wav_out, int32_t flags);
+void pk_pqmf_destroy(pk_pqmf* q);
+
+/* ------------------------------------------------------- MelGAN / multi-band MelGAN generator */
+/* The generator of MelGAN (Kumar et al. 2019) and of multi-band MelGAN (Yang et al. 2020) with the module layout of the
+ * usual MelGANGenerator, as recalled; NEITHER THE PARAMETER NAMES NOR THIS LAYOUT COULD BE CHECKED AGAINST A RELEASED
+ * CHECKPOINT.  With ch_i = channels >> i, a = LeakyReLU(negative_slope), S = stacks, R = ReflectionPad1d:
+ *   x = Conv1D(in_channels -> channels, kernel_size)(R((kernel_size - 1) / 2)(mel))                    "melgan.1"
+ *   per stage i (scale s_i), q_i = 2 + i (2 + S):
+ *     x = Conv1DTranspose(ch_i -> ch_(i+1), 2 s_i, stride s_i, padding s_i / 2 + s_i % 2,
+ *                         output_padding s_i % 2)(a(x))                                                "melgan.{q_i + 1}"
+ *     per stack j = 0 ... S - 1, d = stack_kernel_size ^ j:
+ *       t = Conv1D(k = stack_kernel_size, dilation d)(R((k - 1) / 2 d)(a(x)))                          "melgan.{q_i + 2 + j}.stack.2"
+ *       x = Conv1D(1x1)(a(t)) + Conv1D(1x1)(x)                   "melgan.{q_i + 2 + j}.stack.4", "melgan.{q_i + 2 + j}.skip_layer"
+ *   y = Conv1D(ch_last -> out_channels, kernel_size)(R(...)(a(x)))                                     "melgan.{2 + n (2 + S) + 2}"
+ *   y = tanh(y) with use_final_nonlinear_activation
+ * Weights: Conv1D (C_out, C_in, k), Conv1DTranspose (C_in, C_out, k); ".weight", or ".weight_g" / ".weight_v" folded at
+ * finalize (norm over all axes but 0).  A stack is three launches of the HiFi-GAN convolution kernel: the dilated
+ * convolution under the reflecting boundary rule, the skip convolution (slope 1: LeakyReLU is the identity), the 1x1
+ * convolution of a(t) whose epilogue adds the skip.
+ * Envelope (else PK_EUNSUPPORTED, the message names the limit): in_channels 1 ... 512; out_channels 1 ... 16; kernel_size
+ * odd 3 ... 11; 1 ... 6 stages with scales 2 ... 16; every ch_i a multiple of 8 in 8 ... 512; stacks 1 ... 6,
+ * stack_kernel_size odd 3 ... 7 with (k - 1) / 2 * k^(S - 1) <= 64; bias = 1; reflection padding, no causal convolutions.
+ * Reflection needs its pad smaller than the length it pads at every padded convolution: pk_mgan_min_frames is the
+ * smallest admissible frame count (4 for the defaults); pk_mgan_infer returns PK_EINVAL naming it for a shorter utterance. */
+#define PK_MGAN_MAX_STAGES 6
+typedef struct pk_mgan pk_mgan;
+typedef struct {
+    int32_t in_channels;                  /* 80 */
+    int32_t out_channels;                 /* 1; multi-band: 4 */
+    int32_t channels;                     /* 512 */
+    int32_t kernel_size;                  /* 7 */
+    int32_t n_upsample;                   /* 4 */
+    int32_t upsample_scales[PK_MGAN_MAX_STAGES];   /* 8, 8, 2, 2 */
+    int32_t stacks;                       /* 3 */
+    int32_t stack_kernel_size;            /* 3 */
+    int32_t bias;                         /* 1 */
+    int32_t use_final_nonlinear_activation;   /* 1 */
+    float negative_slope;                 /* 0.2 */
+} pk_mgan_cfg;
+int pk_mgan_create(pk_ctx* ctx, const pk_mgan_cfg* cfg, pk_mgan** out);
+int pk_mgan_set_param(pk_mgan* h, const char* name, const float* data, const int64_t* shape, int32_t ndim);
+int pk_mgan_finalize(pk_mgan* h);
+/* PK_PWG_MATH_F16X3 (default; block scales as pk_hfg_set_math) or PK_PWG_MATH_F32.  PK_PWG_MATH_BF16X3: PK_EUNSUPPORTED. */
+int pk_mgan_set_math(pk_mgan* h, int32_t mode);
+int pk_mgan_set_normalizer(pk_mgan* h, const float* mu, const float* sigma, int32_t n);
+/* The smallest frame count pk_mgan_infer accepts for an utterance. */
+int32_t pk_mgan_min_frames(const pk_mgan* h);
+/* Attach a synthesis bank (NULL: detach): requires subbands == out_channels (else PK_EINVAL).  pk_mgan_infer then writes
+ * the full-band waveform, frames * hop * subbands samples per utterance, straight from the sub-band buffer.  The bank must
+ * outlive the attachment and live on the same context. */
+int pk_mgan_set_pqmf(pk_mgan* h, pk_pqmf* pqmf);
+/* mel: packed (sum frames, in_channels); frames (B, host) >= pk_mgan_min_frames each (else PK_EINVAL).  out: per utterance
+ * (out_channels, frames[b] * hop) channel-major, the blocks packed in order -- the waveform for out_channels = 1 -- or,
+ * with a bank attached, the packed full-band waveform (sum frames * hop * subbands).  An utterance's samples are
+ * bit-identical alone, in any batch and at any position in it.  Plain launches, no atomics.  The workspace is sized per
+ * call; a call that would need more than 16 GiB of activations returns PK_ENOMEM (split the batch; chunking one long
+ * utterance is not implemented).  flags: PK_APPLY_NORMALIZER, PK_HOST_IO (mel and out are host pointers; synchronous). */
+int pk_mgan_infer(pk_mgan* h, const float* mel, const int32_t* frames, int32_t B, float* out, int32_t flags);
+/* Test tap: the output of stage `stage` (0 ... n_upsample - 1, after its last stack) of utterance b of the last
+ * pk_mgan_infer, to HOST as (channels >> (stage + 1), frames[b] * scales up to the stage); n_floats = that many (else
+ * PK_ESHAPE).  Runs the stack again over that utterance.  PK_ESTATE without a pk_mgan_infer since the parameters were set. */
+int pk_mgan_debug_read(pk_mgan* h, int32_t stage, int32_t b, float* host_out, int64_t n_floats);
+/* Test tap of one launch, to HOST as (C_out, positions).  Launches in order: the input convolution; per stage the transposed
+ * convolution, then per stack t, the skip convolution, x'; last the output convolution (out_channels, frames[b] * hop): the
+ * sub-bands, also when a bank is attached. */
+int pk_mgan_debug_conv(pk_mgan* h, int32_t launch, int32_t b, float* host_out, int64_t n_floats);
+void pk_mgan_destroy(pk_mgan* h);
+
 /* ------------------------------------------------- masked L1 + SSIM of mel pairs */
 /* The two spectrogram terms of the SpeedySpeech evaluator (speedyspeech_updater.py:119-140) in one pass over both
  * images, and parakeet/modules/ssim.py:21-61 (channel = 1) as a metric of its own.

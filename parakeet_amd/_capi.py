@@ -157,6 +157,18 @@ class HfgCfg(C.Structure):
                  ("negative_slope", C.c_float)])
 
 
+class MganCfg(C.Structure):
+    """pk_mgan_cfg"""
+    _fields_ = ([(n, C.c_int32) for n in ("in_channels", "out_channels", "channels", "kernel_size", "n_upsample")] +
+                [("upsample_scales", C.c_int32 * 6), ("stacks", C.c_int32), ("stack_kernel_size", C.c_int32), ("bias", C.c_int32),
+                 ("use_final_nonlinear_activation", C.c_int32), ("negative_slope", C.c_float)])
+
+
+class PqmfCfg(C.Structure):
+    """pk_pqmf_cfg"""
+    _fields_ = [("subbands", C.c_int32), ("taps", C.c_int32), ("cutoff_ratio", C.c_float), ("beta", C.c_float)]
+
+
 class OpGemmCfg(C.Structure):
     """pk_op_gemm_cfg"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "res", "a_amax", "a2_amax", "rowvalid", "out_rowmap", "C", "C2",
@@ -349,6 +361,22 @@ def _declare(lib):
         "pk_hfg_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_hfg_debug_conv": (C.c_int, [vp, i32, i32, f32p, i64]),
         "pk_hfg_destroy": (None, [vp]),
+        "pk_pqmf_create": (C.c_int, [vp, C.POINTER(PqmfCfg), C.POINTER(vp)]),
+        "pk_pqmf_filters": (C.c_int, [vp, f32p, f32p, i64]),
+        "pk_pqmf_analysis": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_pqmf_synthesis": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_pqmf_destroy": (None, [vp]),
+        "pk_mgan_create": (C.c_int, [vp, C.POINTER(MganCfg), C.POINTER(vp)]),
+        "pk_mgan_set_param": (C.c_int, [vp, cstr, f32p, i64p, i32]),
+        "pk_mgan_finalize": (C.c_int, [vp]),
+        "pk_mgan_set_math": (C.c_int, [vp, i32]),
+        "pk_mgan_set_normalizer": (C.c_int, [vp, f32p, f32p, i32]),
+        "pk_mgan_min_frames": (i32, [vp]),
+        "pk_mgan_set_pqmf": (C.c_int, [vp, vp]),
+        "pk_mgan_infer": (C.c_int, [vp, f32p, i32p, i32, f32p, i32]),
+        "pk_mgan_debug_read": (C.c_int, [vp, i32, i32, f32p, i64]),
+        "pk_mgan_debug_conv": (C.c_int, [vp, i32, i32, f32p, i64]),
+        "pk_mgan_destroy": (None, [vp]),
         "pk_mel_loss_run": (C.c_int, [vp, f32p, f32p, i32p, i32p, i32, i32, i32, C.c_void_p, f32p, i32]),
         "pk_pair_loss_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i64, i64, i32p, i32, i32, C.c_void_p, i32]),
         "pk_bce_logits_run": (C.c_int, [vp, f32p, f32p, i64p, i64p, i32p, i32, C.c_float, C.c_void_p, i32]),

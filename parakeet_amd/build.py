@@ -37,7 +37,8 @@ _UNROLL_ALL = ["-mllvm", "-pragma-unroll-threshold=2000000"]
 # and pitch.hip, whose R difference-and-FMA chains per work item are the same kind of lines, and align.hip, whose logf of a lane's
 # C columns are C independent fp32 chains, and stats.hip, whose STATS_UNROLL loaded rows per slot are independent conversions,
 # and rfft.hip, whose complex butterflies are pairs of scalar lines on .x and .y, and stoi.hip, whose clean / degraded values
-# and x / y float64 chains run side by side in every kernel
+# and x / y float64 chains run side by side in every kernel; melgan.hip instantiates hifigan.hip's kernel and takes its flags,
+# and pqmf.hip's kernels are single fmaf chains of the same scalar kind
 _NO_SLP = ["-fno-slp-vectorize"]
 # dtw.hip: the local cost of feature mode is DEFINED as separate float64 operations (pk_dtw.h); device code is contracted into
 # fused multiply-adds by default.  Its R independent float64 chains per lane are the same kind of scalar lines as align.hip's.
@@ -50,11 +51,11 @@ _NO_CONTRACT = ["-ffp-contract=off"]
 FILE_FLAGS = {"wf_layer.hip": _UNROLL_ALL, "ffn_planes.hip": _UNROLL_ALL, "ops.hip": _NO_SLP, "speedyspeech.hip": _NO_SLP,
               "tts.hip": _NO_SLP, "tts_teacher.hip": _NO_SLP, "taco2.hip": _NO_SLP, "pwg_gen.hip": _NO_SLP, "mel_loss.hip": _NO_SLP,
               "pwg_disc.hip": _NO_SLP, "spk_loss.hip": _NO_SLP, "resample.hip": _NO_SLP, "pitch.hip": _NO_SLP, "align.hip": _NO_SLP, "stats.hip": _NO_SLP,
-              "rfft.hip": _NO_SLP, "hifigan.hip": _NO_SLP,
+              "rfft.hip": _NO_SLP, "hifigan.hip": _NO_SLP, "melgan.hip": _NO_SLP, "pqmf.hip": _NO_SLP,
               "dtw.hip": _NO_SLP + _NO_CONTRACT, "stoi.hip": _NO_SLP + _NO_CONTRACT, "iir.hip": _NO_SLP + _NO_CONTRACT,
               "pvoc.hip": _NO_SLP + _NO_CONTRACT}
 ISA_DIR = os.path.join(CSRC, "_isa")   # the product build's device assembly, one .s per source (kept for tools/pk_opsel_lint.py and the ISA tools)
-SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "rfft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "edit.hip", "stoi.hip", "iir.hip", "pvoc.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "hifigan.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
+SOURCES = ["pk_ctx.cpp", "pwg.hip", "pwg_gen.hip", "gemm.hip", "fft.hip", "fs2.hip", "ffn_planes.hip", "waveflow.hip", "wf_layer.hip", "speedyspeech.hip", "tts.hip", "tts_teacher.hip", "gst.hip", "taco2.hip", "spk.hip", "spk_loss.hip", "rowgemm.hip", "mel.hip", "istft.hip", "rfft.hip", "resample.hip", "pitch.hip", "trim.hip", "align.hip", "dtw.hip", "edit.hip", "stoi.hip", "iir.hip", "pvoc.hip", "stats.hip", "stft_dist.hip", "pwg_disc.hip", "hifigan.hip", "melgan.hip", "pqmf.hip", "mel_loss.hip", "seq_loss.hip", "ops.hip"]
 
 
 def hipcc():

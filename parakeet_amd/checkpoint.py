@@ -242,6 +242,26 @@ def load_hifigan(config, checkpoint, stats):
     return HiFiGANInference(ZScore(mu, sigma), vocoder)
 
 
+def load_melgan(config, checkpoint, stats):
+    """A MelGAN or multi-band MelGAN vocoder from a recipe's yaml (``generator_params``), a snapshot archive
+    (``generator_params``) and the mel statistics, as ``load_hifigan``: returns ``MelGANInference``.  With ``out_channels`` > 1
+    the bank is built from the yaml's ``pqmf_params`` (or the defaults); ``pqmf.*`` keys of the archive -- the bank's filters,
+    which the engine computes itself -- are ignored.  The parameter names the engine expects are listed in
+    parakeet_amd/melgan.py; they could not be checked against a released checkpoint."""
+    from .melgan import PQMF, MelGANGenerator, MelGANInference
+    from .normalizer import ZScore
+    cfg = _config(config)
+    vocoder = MelGANGenerator(**cfg["generator_params"])
+    vocoder.set_state_dict({k: v for k, v in load_params(checkpoint, "generator_params").items() if not k.startswith("pqmf.")})
+    vocoder.remove_weight_norm()
+    vocoder.eval()
+    pqmf = None
+    if vocoder.out_channels > 1:
+        pqmf = PQMF(**dict({"subbands": vocoder.out_channels}, **(cfg.get("pqmf_params") or {})))
+    mu, sigma = load_stats(stats)
+    return MelGANInference(ZScore(mu, sigma), vocoder, pqmf)
+
+
 def load_pwg_discriminator(config, checkpoint):
     """The discriminator a Parallel WaveGAN snapshot carries beside its generator (``models['discriminator']`` of
     examples/parallel_wavegan/baker/train.py, saved as ``discriminator_params``): returns ``PWGDiscriminator`` built from the

@@ -266,6 +266,46 @@ def hifigan_state(cfg=None, seed=11, weight_norm=False):
     return st
 
 
+MELGAN = dict(   # the usual MelGANGenerator defaults at hop 256
+    in_channels=80, out_channels=1, kernel_size=7, channels=512, bias=True, upsample_scales=(8, 8, 2, 2), stack_kernel_size=3,
+    stacks=3, nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, pad="ReflectionPad1d",
+    pad_params={}, use_final_nonlinear_activation=True, use_weight_norm=True, use_causal_conv=False)
+MB_MELGAN = dict(MELGAN, out_channels=4, channels=384, upsample_scales=(8, 4, 2), stacks=4)   # x 4 bands: hop 256
+
+
+def melgan_state(cfg=None, seed=12, weight_norm=False):
+    """Seeded MelGANGenerator state dict under the names of parakeet_amd/melgan.py (as recalled; not checked against a
+    released checkpoint): weights N(0, 1) / sqrt(fan_in), x 0.7 on the two 1x1 convolutions whose outputs a stack adds (so
+    that a stack's output stays at its input's size), biases 0.1 N(0, 1).  ``weight_norm``: weight_g (C, 1, 1) with the
+    rows' norms times a factor in [0.8, 1.25], weight_v the direction at another length."""
+    cfg = dict(MELGAN, **(cfg or {}))
+    rng = np.random.default_rng(seed)
+    st = {}
+
+    def put(name, shape, fan_in, gain=1.0, transposed=False):
+        w = (rng.standard_normal(shape) * gain / math.sqrt(fan_in)).astype(np.float32)
+        if weight_norm:
+            norm = np.sqrt((w.astype(np.float64).reshape(shape[0], -1) ** 2).sum(1))
+            st[name + ".weight_g"] = (norm * rng.uniform(0.8, 1.25, size=shape[0])).astype(np.float32).reshape(-1, 1, 1)
+            st[name + ".weight_v"] = (w * rng.uniform(0.5, 2.0, size=(shape[0], 1, 1))).astype(np.float32)
+        else:
+            st[name + ".weight"] = w
+        st[name + ".bias"] = (0.1 * rng.standard_normal(shape[1] if transposed else shape[0])).astype(np.float32)
+
+    ch, k, S, sk = cfg["channels"], cfg["kernel_size"], cfg["stacks"], cfg["stack_kernel_size"]
+    put("melgan.1", (ch, cfg["in_channels"], k), cfg["in_channels"] * k)
+    n = len(cfg["upsample_scales"])
+    for i, s in enumerate(cfg["upsample_scales"]):
+        q, cin, c = 2 + i * (2 + S), ch >> i, ch >> (i + 1)
+        put(f"melgan.{q + 1}", (cin, c, 2 * s), 2 * cin, transposed=True)   # two taps reach an output
+        for j in range(S):
+            put(f"melgan.{q + 2 + j}.stack.2", (c, c, sk), c * sk)
+            put(f"melgan.{q + 2 + j}.stack.4", (c, c, 1), c, 0.7)
+            put(f"melgan.{q + 2 + j}.skip_layer", (c, c, 1), c, 0.7)
+    put(f"melgan.{2 + n * (2 + S) + 2}", (cfg["out_channels"], ch >> n, k), (ch >> n) * k)
+    return st
+
+
 PWG_DISC_LJSPEECH = dict(   # discriminator_params of examples/parallel_wavegan/baker/conf/default.yaml
     in_channels=1, out_channels=1, kernel_size=3, layers=10, conv_channels=64, dilation_factor=1,
     nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2}, bias=True, use_weight_norm=True)
